@@ -11,6 +11,19 @@ ranks), lower is better. One timed step = one full iteration of the reference's 
 the 1e4 x 112 fp32 partial sums (``--strategy``: allreduce, or the reference's headline
 regroup -> average at owner -> allgather), normalize, centroid operand prepare.
 
+A plain run (``--gpus 1 --steps K --warmup W``) does only what that headline needs: set up,
+warm up, time the K steps, write the outputs (``--dump-outputs DIR``) and print the result
+line. Everything below -- the RCCL pre-flight, the nested MF-SGD / PCA / LDA records and the
+objective pass after timing (``mean_sq_dist``) -- runs only with ``--full``.
+
+``--dump-outputs DIR`` writes what the last timed step left for a caller of the mapper:
+``DIR/centroids.npy`` (K x d float32, the model after that step) and
+``DIR/labels_sample.npy`` (rank 0's assignment of that step at a fixed, seeded sample of
+its points, float32; absent in rotation mode, where a step leaves block-relative labels).
+Points and initial centroids are seeded, and with this option the last timed step starts
+again from the initial centroids (see ``bench_kmeans``), so two builds run with the same
+arguments can be compared array for array.
+
 Nested ``pca`` / ``lda`` records (on GPUs; ``--extras off`` skips them): BASELINE configs 4
 and 5 -- one PCA correlation pass over N = 1e8 x d = 1000 (MFMA SYRK partial result +
 allreduce + fp64 eig) and LDA-CGS over 1M docs x 1M vocab x 1000 topics with the push-pull
@@ -27,7 +40,7 @@ ranks) -- BASELINE.md's protocol; nested records time >= 10 iterations by defaul
 record that hangs past its guard leaves the headline line printed and exits 124.
 
 Usage:
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   With N > 1 and no torchrun environment, the parent process spawns the N ranks itself
   (before anything touches the GPU); under ``torch.distributed.run`` the ranks come from
   RANK / LOCAL_RANK / WORLD_SIZE.
@@ -52,6 +65,11 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the RCCL pre-flight, the nested MF-SGD / PCA / LDA records (--sgd, --extras) "
+                         "and the objective pass after timing; a plain run measures the K-means headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy")
     ap.add_argument("--points", type=float, default=1e8, help="total points (strong scaling)")
     ap.add_argument("--centroids", type=int, default=10000)
     ap.add_argument("--dim", type=int, default=100)
@@ -60,7 +78,7 @@ def parse_args(argv=None):
     ap.add_argument("--backend", default=None, help="override (e.g. gloo to rehearse >1 rank on the CPU)")
     ap.add_argument("--graph", action="store_true", help="replay each iteration's kernels from HIP graphs")
     ap.add_argument("--sgd", choices=("auto", "on", "off"), default="auto",
-                    help="nested MF-SGD record (auto: on when the ranks run on GPUs)")
+                    help="nested MF-SGD record, with --full (auto: on when the ranks run on GPUs)")
     ap.add_argument("--sgd-users", type=int, default=480189)
     ap.add_argument("--sgd-items", type=int, default=17770)
     ap.add_argument("--sgd-ratings", type=int, default=100480507)
@@ -80,7 +98,7 @@ def parse_args(argv=None):
                     help="wall-clock bound (s) on the nested MF-SGD record; past it rank 0 prints the "
                          "K-means line with an sgd error and every rank exits")
     ap.add_argument("--extras", choices=("auto", "on", "off"), default="auto",
-                    help="nested PCA (BASELINE config 4) and LDA (config 5) records (auto: on GPUs)")
+                    help="nested PCA (BASELINE config 4) and LDA (config 5) records, with --full (auto: on GPUs)")
     ap.add_argument("--pca-n", type=float, default=1e8)
     ap.add_argument("--pca-d", type=int, default=1000)
     ap.add_argument("--pca-steps", type=int, default=10)
@@ -98,7 +116,10 @@ def parse_args(argv=None):
     ap.add_argument("--metrics-jsonl", default="", help="per-iteration phase/bytes records (JSONL)")
     ap.add_argument("--preflight-timeout", type=float, default=120.0,
                     help="wall-clock bound (s) on the RCCL pre-flight (world / devices / battery / bandwidth)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full and (args.sgd == "on" or args.extras == "on"):
+        ap.error("--sgd on / --extras on ask for nested records, which run only with --full")
+    return args
 
 
 # ----------------------------------------------------------------------------- spawning
@@ -283,6 +304,12 @@ def bench_kmeans(args, comm, torch):
     metrics = Metrics(rank=rank, path=args.metrics_jsonl or None)
     m = KMeansCollectiveMapper(comm, cfg, metrics=metrics)
     m.init_model(_Reader())
+    # --dump-outputs: the last timed step starts again from the seeded initial model (a K x d copy
+    # and an operand prepare, microseconds). Free-running steps are not reproducible enough to
+    # compare builds: after 12 of them at the default size two runs of one build differed by up
+    # to 5 % in the centroids and in 6 % of the labels (near-tied points change cluster on any
+    # rounding difference, and the next iteration amplifies that).
+    restore = m.c.clone() if args.dump_outputs and args.strategy != "rotation" else None
     for it in range(args.warmup):
         m.step(it)
     sync(comm, torch)
@@ -292,6 +319,9 @@ def bench_kmeans(args, comm, torch):
     t0 = time.perf_counter()
     clock.mark()
     for it in range(args.steps):
+        if restore is not None and it == args.steps - 1:
+            m.c.copy_(restore)
+            m.op = K.prepare(m.c[:args.centroids], m.dp, m.op)
         m.step(args.warmup + it)
         clock.mark()
     sync(comm, torch)
@@ -301,13 +331,18 @@ def bench_kmeans(args, comm, torch):
     coll = m.metrics.summary()["collectives"]
     elapsed = reduce_max(comm, torch, elapsed)
     sec_per_iter = elapsed / args.steps
-    # objective after timing (one extra assign pass, outside the timed region) as a sanity value
-    if args.strategy == "rotation":  # the model lives in rotating blocks: gather it first
-        m.op = K.prepare(m._rotation_gather().contiguous(), m.dp)
-    _, obj = K.assign(m.X, m.op, sums=None, want_objective=True, variant=cfg.variant)
-    o = obj.reshape(1).to(comm.device, torch.float64)
-    if P > 1:
-        comm.all_reduce(o)
+    if args.dump_outputs:
+        dump_outputs(args, comm, torch, m)
+    mean_sq_dist = None
+    if args.full:
+        # objective after timing (one extra assign pass, outside the timed region) as a sanity value
+        if args.strategy == "rotation":  # the model lives in rotating blocks: gather it first
+            m.op = K.prepare(m._rotation_gather().contiguous(), m.dp)
+        _, obj = K.assign(m.X, m.op, sums=None, want_objective=True, variant=cfg.variant)
+        o = obj.reshape(1).to(comm.device, torch.float64)
+        if P > 1:
+            comm.all_reduce(o)
+        mean_sq_dist = float(o.item()) / N
     flops = 2.0 * N * args.centroids * args.dim
     sync_bytes = sum(v["bytes"] for v in coll.values()) / max(args.steps, 1)
     rec = {
@@ -333,12 +368,40 @@ def bench_kmeans(args, comm, torch):
         "sync_bytes_per_iter": int(sync_bytes),
         "collectives": {k: {"calls": v["calls"], "ms": round(v["s"] * 1e3, 3), "bytes": v["bytes"]}
                         for k, v in coll.items()},
-        "mean_sq_dist": float(o.item()) / N,
+        "mean_sq_dist": mean_sq_dist,  # --full only
         "kernel_variant": cfg.variant,
         "hip_graph": bool(args.graph),
     }
     del m
     return rec
+
+
+DUMP_LABELS = 1 << 20  # sampled assignments written by --dump-outputs (4 MB as float32)
+
+
+def dump_outputs(args, comm, torch, m) -> None:
+    """``--dump-outputs DIR``: what the last timed step left for a caller of the mapper, as
+    float32 ``.npy`` files written by rank 0 -- the centroids (K x d, 4 MB at the default
+    size; identical on every rank after the model sync) and this rank's labels of that step
+    at a fixed, seeded sample of its points (all of them when there are fewer)."""
+    import numpy as np
+
+    k = args.centroids
+    rotation = args.strategy == "rotation"
+    c = m._rotation_gather() if rotation else m.c  # a collective in rotation mode: every rank calls it
+    if comm.rank != 0:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    np.save(os.path.join(args.dump_outputs, "centroids.npy"), c[:k].float().cpu().numpy())
+    if not rotation:
+        n = m.lab.numel()
+        if n > DUMP_LABELS:
+            g = torch.Generator().manual_seed(12345)
+            idx = torch.randint(0, n, (DUMP_LABELS,), generator=g).sort().values.to(m.lab.device)
+            lab = m.lab[idx]
+        else:
+            lab = m.lab
+        np.save(os.path.join(args.dump_outputs, "labels_sample.npy"), lab.float().cpu().numpy())
 
 
 def _coll_breakdown(metrics, iters: int, comm, torch) -> dict:
@@ -809,8 +872,16 @@ def run(args) -> int:
         return rccl_preflight(a, c, t)
 
     pre = {}
-    _nested(pre, "rccl", barrier_and_preflight, args.preflight_timeout, args, comm, torch)
+    if args.full:
+        _nested(pre, "rccl", barrier_and_preflight, args.preflight_timeout, args, comm, torch)
+    elif world > 1:
+        comm.barrier()
     rec = bench_kmeans(args, comm, torch)
+    if not args.full:  # a plain run: the headline record alone
+        if comm.rank == 0:
+            print(json.dumps(rec), flush=True)
+        shutdown()
+        return 0
     rec["rccl"] = pre["rccl"]
     if comm.device.type == "cuda":
         torch.cuda.empty_cache()

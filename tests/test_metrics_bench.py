@@ -125,12 +125,43 @@ def test_bench_self_spawns_ranks():
     assert "sgd" not in rec  # auto: CPU ranks skip the SGD record
 
 
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """Without --full the run measures the K-means headline alone (no pre-flight, no nested
+    record, no objective pass), --steps sets the timed steps, and --dump-outputs writes the
+    last step's centroids and sampled labels as float32 .npy files that a second run with
+    the same arguments reproduces (seeded points and initial centroids)."""
+    import numpy as np
+
+    args = ["--gpus", "1", "--points", "5000", "--centroids", "128", "--steps", "3", "--warmup", "1"]
+    recs = [_run_bench(args + ["--dump-outputs", str(tmp_path / name)]) for name in ("a", "b")]
+    rec = recs[0]
+    assert rec["metric"].startswith("sec/iteration K-means") and rec["unit"] == "s/iter"
+    assert rec["higher_is_better"] is False and rec["dtype"] in ("bf16", "fp32")
+    assert rec["steps"] == 3 and rec["step_s"]["n"] == 3 and rec["value"] > 0
+    assert rec["ms_per_step"] == pytest.approx(rec["value"] * 1e3, abs=1e-3)
+    assert rec["mean_sq_dist"] is None
+    assert not {"rccl", "sgd", "pca", "lda"} & set(rec)
+    a, b = ({n: np.load(tmp_path / d / f"{n}.npy") for n in ("centroids", "labels_sample")} for d in ("a", "b"))
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["centroids.npy", "labels_sample.npy"]
+    assert a["centroids"].shape == (128, 100) and a["labels_sample"].shape == (5000,)
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert 0 <= a["labels_sample"].min() and a["labels_sample"].max() < 128
+    assert np.array_equal(a["labels_sample"], b["labels_sample"])
+    assert np.allclose(a["centroids"], b["centroids"], rtol=1e-5, atol=1e-3)
+
+
+def test_bench_nested_records_need_full():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--sgd", "on"],
+                       capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert r.returncode == 2 and "--full" in r.stderr
+
+
 def test_bench_rccl_preflight_three_ranks():
     """The self-diagnosing pre-flight at P=3 over gloo: world size seen by
     every rank, per-rank device records, a passing collective battery, a 64 MB all-reduce
     bus bandwidth and one ring send/recv per rotation channel (distinct strides at P=3)."""
-    rec = _run_bench(["--gpus", "3", "--points", "3e4", "--centroids", "128", "--backend", "gloo", "--steps", "2",
-                      "--warmup", "1"])
+    rec = _run_bench(["--full", "--gpus", "3", "--points", "3e4", "--centroids", "128", "--backend", "gloo",
+                      "--steps", "2", "--warmup", "1"])
     r = rec["rccl"]
     assert r["world"] == 3 and r["world_seen"] == [3, 3, 3] and r["backend"] == "gloo"
     assert [x["rank"] for x in r["ranks"]] == [0, 1, 2]
@@ -145,7 +176,7 @@ def test_bench_rccl_preflight_three_ranks():
 
 
 def test_bench_single_rank_with_sgd_record():
-    rec = _run_bench(["--gpus", "1", "--points", "1e4", "--centroids", "128", "--steps", "2", "--warmup", "1",
+    rec = _run_bench(["--full", "--gpus", "1", "--points", "1e4", "--centroids", "128", "--steps", "2", "--warmup", "1",
                       "--sgd", "on", "--sgd-users", "2000", "--sgd-items", "300", "--sgd-ratings", "20000",
                       "--sgd-rank", "16", "--sgd-epochs", "2"])
     assert rec["n_gpus"] == 1 and rec["metric"].startswith("sec/iteration K-means")
@@ -158,14 +189,14 @@ def test_bench_sgd_guard_keeps_headline_line():
     """A nested MF-SGD record that exceeds --sgd-timeout (a hung rotation peer on a real
     node) still yields exactly one JSON line: the measured K-means record with sgd.error,
     and the run exits non-zero (124) so the hang is never reported as a clean run."""
-    rec = _run_bench(["--gpus", "2", "--points", "2e4", "--centroids", "128", "--backend", "gloo", "--steps", "2",
-                      "--warmup", "1", "--sgd", "on", "--sgd-users", "2000", "--sgd-items", "300",
+    rec = _run_bench(["--full", "--gpus", "2", "--points", "2e4", "--centroids", "128", "--backend", "gloo",
+                      "--steps", "2", "--warmup", "1", "--sgd", "on", "--sgd-users", "2000", "--sgd-items", "300",
                       "--sgd-ratings", "20000", "--sgd-rank", "16", "--sgd-timeout", "0.01"], rc=124)
     assert rec["n_gpus"] == 2 and rec["value"] > 0
     assert "timeout" in rec["sgd"]["error"]
 
 
-_TINY = ["--points", "3e4", "--centroids", "128", "--backend", "gloo", "--steps", "10", "--warmup", "1",
+_TINY = ["--full", "--points", "3e4", "--centroids", "128", "--backend", "gloo", "--steps", "10", "--warmup", "1",
          "--sgd", "on", "--sgd-users", "3000", "--sgd-items", "400", "--sgd-ratings", "30000", "--sgd-rank", "16",
          "--sgd-epochs", "10", "--extras", "on", "--pca-n", "6000", "--pca-d", "24", "--pca-steps", "10",
          "--lda-docs", "600", "--lda-vocab", "900", "--lda-topics", "16", "--lda-len", "20", "--lda-iters", "10"]
@@ -230,7 +261,7 @@ def test_bench_full_records_eight_ranks():
 def test_bench_single_rank_lda_records_collective_cost():
     """At P=1 the push-pull headline runs the pull / delta / push passes (never the
     aliased local server, which is only a nested extra on GPUs)."""
-    rec = _run_bench(["--gpus", "1", "--points", "1e4", "--centroids", "128", "--steps", "2", "--warmup", "1",
+    rec = _run_bench(["--full", "--gpus", "1", "--points", "1e4", "--centroids", "128", "--steps", "2", "--warmup", "1",
                       "--sgd", "off", "--extras", "on", "--pca-n", "3000", "--pca-d", "16", "--pca-steps", "2",
                       "--lda-docs", "300", "--lda-vocab", "500", "--lda-topics", "16", "--lda-len", "20",
                       "--lda-iters", "2"])
@@ -281,8 +312,8 @@ def test_bench_two_ranks_on_one_gpu_all_records(cuda):
     """Every nested record at P = 2 with both ranks' kernels on the GPU (gloo with host
     staging: RCCL refuses two ranks per device): the multi-rank device paths (rotation
     rings, sparse push / pull rows, PCA broadcast) run before an 8-GPU node sees them."""
-    rec = _run_bench(["--gpus", "2", "--backend", "gloo", "--points", "2e5", "--centroids", "256", "--steps", "3",
-                      "--warmup", "1", "--sgd", "on", "--sgd-users", "20000", "--sgd-items", "3000",
+    rec = _run_bench(["--full", "--gpus", "2", "--backend", "gloo", "--points", "2e5", "--centroids", "256",
+                      "--steps", "3", "--warmup", "1", "--sgd", "on", "--sgd-users", "20000", "--sgd-items", "3000",
                       "--sgd-ratings", "400000", "--sgd-epochs", "3", "--extras", "on", "--pca-n", "2e5",
                       "--pca-d", "200", "--pca-steps", "3", "--lda-docs", "5000", "--lda-vocab", "8000",
                       "--lda-topics", "256", "--lda-len", "40", "--lda-iters", "3"])

@@ -147,7 +147,7 @@ def test_rccl_watchdog_fails_the_gang_and_restart_resumes(tmp_path):
 def test_bench_spawns_rccl_ranks():
     P = P_LIST[-1]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(P), "--points", "4e6",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(P), "--points", "4e6",
                         "--steps", "3", "--warmup", "1", "--sgd-ratings", "4000000", "--sgd-epochs", "2"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]

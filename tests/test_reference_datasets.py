@@ -3,7 +3,9 @@
 Where the reference ships expected outputs (daal_reg groundTruth, daal_naive testTruth) we
 compare to them (daal_nn's groundTruth: tests/test_reference_fixtures.py); elsewhere we
 compare to sklearn on the same file ("parity unpinned" for DAAL's exact numbers: the DAAL
-native library is not available). Skipped when the reference tree is absent (e.g. on the GPU box)."""
+native library is not available). The smallest fixtures (daal_em, the LDA-CVB sample; a few
+KB) are stored under tests/golden/datasets in the reference's directory layout (``golden``);
+the others are read from a reference checkout (``P``), and their tests skip without one."""
 import os
 
 import pytest
@@ -19,11 +21,17 @@ from harp_amd.models import kmeans_csr as KC
 from harp_amd.utils import datasets as DS
 
 ROOT = "/root/reference/datasets"
-pytestmark = pytest.mark.skipif(not os.path.isdir(ROOT), reason="reference datasets not present")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "datasets")
 
 
 def P(*a):
+    if not os.path.isdir(ROOT):
+        pytest.skip("reference datasets not present")
     return os.path.join(ROOT, *a)
+
+
+def golden(*a):
+    return os.path.join(GOLDEN, *a)
 
 
 def test_linear_regression_vs_ground_truth():
@@ -152,7 +160,7 @@ def test_apriori_file():
 def test_em_gmm_file():
     from sklearn.mixture import GaussianMixture
 
-    X = DS.load_dense_csv(P("daal_em", "batchdense", "train"))
+    X = DS.load_dense_csv(golden("daal_em", "batchdense", "train"))
     m = KF.em_gmm(X, 2, n_iterations=200, accuracy_threshold=1e-10)
     sk = GaussianMixture(2, reg_covar=1e-6, tol=1e-10, max_iter=200, n_init=5, random_state=0).fit(X.numpy())
     assert float(m["loglik"]) >= sk.score(X.numpy()) - 0.05
@@ -198,7 +206,7 @@ def test_lda_cvb_reference_sample_through_cli(tmp_path):
     from harp_amd import cli
     from harp_amd.utils.datasets import load_term_count_docs
 
-    d = os.path.join(ROOT, "tutorial", "lda-cvb", "sample-sparse-data")
+    d = golden("tutorial", "lda-cvb", "sample-sparse-data")
     files = sorted(os.path.join(d, f) for f in os.listdir(d) if f.endswith(".txt"))
     doc, word, cnt = load_term_count_docs(files, os.path.join(d, "sample-sparse-metadata"))
     assert int(doc.max()) + 1 == 12 and int(word.max()) + 1 == 11 and int(cnt.sum()) == 260

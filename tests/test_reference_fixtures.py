@@ -9,7 +9,9 @@ DAAL's own numbers are not in the checkout (the native library is not available)
 "parity" here means agreement with an independent implementation of the same definition,
 except daal_nn (its groundTruth file) and daal_optimization_solvers/lbfgs (the expected
 point the reference mapper hard-codes, LBFGSDaalCollectiveMapper.java:57-58).
-Skipped when the reference tree is absent (e.g. on the GPU box)."""
+The smallest fixtures (cholesky, normalization, outlier, sorting, kernelfunc; under 2 KB
+each) are stored under tests/golden/datasets in the reference's directory layout (``golden``);
+the others are read from a reference checkout (``P``), and their tests skip without one."""
 import math
 import os
 
@@ -22,11 +24,18 @@ from harp_amd.runtime.launcher import launch
 from harp_amd.utils import datasets as DS
 
 ROOT = "/root/reference/datasets"
-pytestmark = pytest.mark.skipif(not os.path.isdir(ROOT), reason="reference datasets not present")
+need_reference = pytest.mark.skipif(not os.path.isdir(ROOT), reason="reference datasets not present")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "datasets")
 
 
 def P(*a):
+    if not os.path.isdir(ROOT):
+        pytest.skip("reference datasets not present")
     return os.path.join(ROOT, *a)
+
+
+def golden(*a):
+    return os.path.join(GOLDEN, *a)
 
 
 def rel(a, b) -> float:
@@ -157,7 +166,7 @@ def test_daal_pivoted_qr():
 
 
 def test_daal_cholesky():
-    A = DS.load_dense_csv(P("daal_cholesky", "train", "cholesky.csv"))
+    A = DS.load_dense_csv(golden("daal_cholesky", "train", "cholesky.csv"))
     L = ST.cholesky(A).numpy()
     ref = np.linalg.cholesky(A.numpy())
     assert rel(L, ref) <= 1e-12 and rel(L @ L.T, A.numpy()) <= 1e-12
@@ -165,7 +174,7 @@ def test_daal_cholesky():
 
 
 def test_daal_normalization():
-    X = DS.load_dense_csv(P("daal_normalization", "train", "normalization.csv"))
+    X = DS.load_dense_csv(golden("daal_normalization", "train", "normalization.csv"))
     A = X.numpy()
     z = ST.normalize_zscore(X).numpy()
     assert rel(z, (A - A.mean(0)) / A.std(0, ddof=1)) <= 1e-12
@@ -179,7 +188,7 @@ def test_daal_outlier():
     """The fixture has two gross outliers (rows 3 and 11, every feature ~26-31). The
     reference runs univariate (DAAL default init: location 0, scatter 1, threshold 3),
     multivariate (Mahalanobis) and BACON detection on it."""
-    X = DS.load_dense_csv(P("daal_outlier", "train", "outlierdetection.csv"))
+    X = DS.load_dense_csv(golden("daal_outlier", "train", "outlierdetection.csv"))
     A = X.numpy()
     bad = {3, 11}
     uni = ST.outliers_univariate(X, init="default").numpy()
@@ -207,7 +216,7 @@ def test_daal_quantile():
 
 
 def test_daal_sorting():
-    X = DS.load_dense_csv(P("daal_sorting", "train", "sorting.csv"))
+    X = DS.load_dense_csv(golden("daal_sorting", "train", "sorting.csv"))
     assert np.array_equal(ST.sort_features(X).numpy(), np.sort(X.numpy(), axis=0))
 
 
@@ -222,10 +231,10 @@ def test_daal_kernelfunc(csr):
     from harp_amd.models import kernels as KF
 
     if csr:
-        X = DS.load_daal_csr(P("daal_kernelfunc", "csrbatch", "kernel_function_csr.csv"))
+        X = DS.load_daal_csr(golden("daal_kernelfunc", "csrbatch", "kernel_function_csr.csv"))
         A = X.to_dense().numpy()
     else:
-        X = DS.load_dense_csv(P("daal_kernelfunc", "densebatch", "kernel_function.csv"))
+        X = DS.load_dense_csv(golden("daal_kernelfunc", "densebatch", "kernel_function.csv"))
         A = X.numpy()
     lin = KF.linear_kernel(X, X, k=1.0, b=0.0)
     lin = lin.to_dense() if lin.layout != torch.strided else lin
@@ -408,6 +417,7 @@ def _exact_tree_counts(src: np.ndarray, dst: np.ndarray, n: int):
     return u3, u5_embeddings
 
 
+@need_reference
 def test_daal_subgraph_web_google():
     """SAHAD / FASCIA color coding on the reference's web-Google graph (875,713 vertices,
     4.32M undirected edges) with its templates u3-1 and u5-2 (daal_subgraph/templates):
@@ -438,6 +448,7 @@ def test_daal_subgraph_web_google():
 MDS = os.path.join(ROOT, "tutorial", "mds_data")
 
 
+@need_reference
 def test_mds_fixture_smacof_matches_numpy():
     """The 4,640-point wdamds fixture (32 row blocks of big-endian shorts; V follows from
     the weights, WDAMDSMapper.java): the first SMACOF steps at T = 0 (B(Z) X + conjugate
@@ -491,6 +502,7 @@ def _mds_worker(comm, blocks_per_rank):
     return {"X": r["X"], "history": r["history"], "stress": r["stress"]}
 
 
+@need_reference
 def test_mds_fixture_distributed_annealing():
     """wda_mds over 4 gloo workers (8 row blocks each, the reference's row partition):
     identical X on every worker through every annealing stage, and the final T = 0 stress
