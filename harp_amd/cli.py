@@ -21,6 +21,8 @@ same parameters as named flags (which win when both are given):
   pagerank  <inputDir> <numUrls> <iters> <maps>   (contrib simplepagerank)
   daal      <algo> <maps> <threads> <memMB> <iters> <inputDir> <workDir> [algo args]
             (harp-daal-interface data_aux/Initialize.java:97-130 common prefix)
+            algo dforest / dforest_reg: decision forest over the workers' row shards (last
+            column = label / target)      [--k classes --n-trees --max-depth --engine]
 
 ``maps`` = number of workers. Outside torchrun the CLI spawns ``maps`` local worker
 processes (RCCL on GPUs when ``maps`` <= visible GPUs, else gloo on CPU); under torchrun
@@ -76,7 +78,8 @@ EXTRA = {  # named-only flags
                ("gamma_iters", int, 29)],
     "sgd": [("num_users", int, 0), ("num_items", int, 0)],
     "ccd": [("num_users", int, 0), ("num_items", int, 0)],
-    "daal": [("k", int, 0), ("method", str, ""), ("label_cols", int, 1)],
+    "daal": [("k", int, 0), ("method", str, ""), ("label_cols", int, 1), ("n_trees", int, 50), ("max_depth", int, 10),
+             ("engine", str, "native")],
     "mds": [("work_dir", str, "harp-work/mds"), ("checkpoint_every", int, 0)],
 }
 
@@ -436,6 +439,24 @@ def _run_daal(comm, cfg):
 
         C0 = kmeans_init(A, cfg["k"] or 10, comm, method=cfg["method"] or "first")
         out = kmeans_sparse(A, C0, cfg["iterations"], comm)
+    elif algo in ("dforest", "dforest_reg"):
+        # one forest over the workers' row shards (last column = label / target); rank 0
+        # writes the packed trees: nodes = (tree, feature, threshold, left), values [N, C]
+        from .models.trees import DecisionForest
+
+        A = A.to(comm.device)
+        cls = algo == "dforest"
+        y = A[:, -1].long() if cls else A[:, -1]
+        k = (cfg["k"] or _allmax(comm, int(y.max()) + 1)) if cls else None
+        forest = DecisionForest("classification" if cls else "regression", n_trees=cfg["n_trees"],
+                                max_depth=cfg["max_depth"], engine=cfg["engine"])
+        forest.fit_distributed(A[:, :-1], y, comm, num_classes=k, mode="rows" if cfg["engine"] == "native" else "trees")
+        tid = torch.cat([torch.full((t.feature.numel(),), float(i), dtype=torch.float64)
+                         for i, t in enumerate(forest.trees)])
+        out = {"nodes": torch.stack([tid, torch.cat([t.feature for t in forest.trees]).double(),
+                                     torch.cat([t.threshold for t in forest.trees]),
+                                     torch.cat([t.left for t in forest.trees]).double()], 1),
+               "values": torch.cat([t.value for t in forest.trees]), "n_trees": len(forest.trees)}
     else:
         raise ValueError(f"unknown daal algo {algo}")
     if comm.rank == 0:

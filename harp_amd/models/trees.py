@@ -6,11 +6,24 @@ regression forests), ``daal_stump``, ``daal_adaboost``, ``daal_brownboost``,
 ``daal_logitboost``; contrib random forests (contrib/.../randomforest, rf, com/rf/fast:
 per-mapper trees on local data, predictions combined by vote through allreduce / reduce).
 
-MI355X design: trees grow level-wise with histogram split search: features are quantile-
-binned once, then per level ONE scatter-add builds (node, feature, bin) histograms of the
-class counts (or gradient sums), a cumulative sum over bins scores every candidate split
-of every node at once, and samples are re-routed with a gather — no per-node host loops
-over samples, so the same code runs on CPU (gloo tests) and on the GPU.
+Trees grow level-wise with histogram split search: features are quantile-binned once, then
+per level (node, feature, bin) histograms of the class counts (or weight / target sums) are
+built, a prefix sum over bins scores every candidate split and the samples are re-routed.
+Two engines train the same ``DecisionTree`` arrays (``feature / threshold / left / value``,
+children numbered in level order, left then right):
+
+* ``engine="torch"`` (default) — plain torch, one tree at a time: per level one fp64
+  ``index_add_`` over an expanded [n, d, C] value tensor builds the histograms, a host loop
+  over the frontier nodes (``.item()`` reads, ``randperm`` feature subsets) picks the splits,
+  and prediction gathers once per depth and tree. It runs anywhere torch does.
+* ``engine="native"`` — ``ops/forest.py`` + ``csrc/forest.hip``: all trees of a batch grow
+  together with the tree arrays on the device and one host read per level; uint8 bins,
+  counter-based bootstrap multiplicities and hashed feature subsets, LDS histograms (exact
+  integer counts for classification with integer multiplicities, fp64 sums otherwise), a
+  wave per (node, feature) split search and a packed-forest prediction kernel. HIP tensors
+  run the kernels, CPU tensors the torch mirror of the same algorithm. ``DecisionForest`` can
+  then also train one model over row shards (``fit_distributed(mode="rows")``: one histogram
+  all-reduce per level). The boosting classes use the torch engine.
 """
 from __future__ import annotations
 
@@ -21,7 +34,38 @@ from typing import List, Optional
 import torch
 
 from ..core.writable import DataInput, DataOutput, Writable
+from ..ops import forest as F
 from ..parallel.comm import Communicator
+
+ENGINES = ("torch", "native")
+
+
+def _n_sub(max_features, d: int) -> Optional[int]:
+    """Features per node of the native engine (None = all), the torch engine's rule."""
+    if not max_features:
+        return None
+    return max_features if isinstance(max_features, int) else max(1, int(math.sqrt(d)))
+
+
+def _trees_from_packed(packed: dict, th: torch.Tensor, proto: "DecisionTree", seeds) -> List["DecisionTree"]:
+    """DecisionTree objects (CPU arrays, as the torch engine leaves them) from ``ops.forest.grow``."""
+    f = packed["feature"]
+    thr = torch.where(f >= 0, th.to(f.device)[f.clamp_min(0), packed["bin"]], torch.zeros((), dtype=torch.float64,
+                                                                                          device=f.device))
+    V = packed["stats"]
+    if proto.task == "classification":
+        val = V / V.sum(1, keepdim=True).clamp_min(1e-300)
+    else:
+        val = (V[:, 1] / V[:, 0].clamp_min(1e-300))[:, None]
+    f, thr, left, val = f.cpu(), thr.cpu(), packed["left"].cpu(), val.cpu()
+    out, a = [], 0
+    for size, seed in zip(packed["sizes"], seeds):
+        t = DecisionTree(proto.task, proto.max_depth, proto.min_leaf, proto.max_features, proto.n_bins,
+                         proto.criterion, seed=seed, engine="native")
+        t.feature, t.threshold, t.left, t.value = f[a:a + size], thr[a:a + size], left[a:a + size], val[a:a + size]
+        out.append(t)
+        a += size
+    return out
 
 
 def _bins(X: torch.Tensor, n_bins: int) -> torch.Tensor:
@@ -38,7 +82,11 @@ class DecisionTree(Writable):
     """CART tree. ``task``: "classification" (gini / entropy) or "regression" (mse)."""
 
     def __init__(self, task: str = "classification", max_depth: int = 8, min_samples_leaf: int = 1,
-                 max_features=None, n_bins: int = 64, criterion: str = "gini", seed: int = 0):
+                 max_features=None, n_bins: int = 64, criterion: str = "gini", seed: int = 0,
+                 engine: str = "torch"):
+        if engine not in ENGINES:
+            raise ValueError(f"engine must be one of {ENGINES} (got {engine!r})")
+        self.engine = engine
         self.task, self.max_depth, self.min_leaf = task, max_depth, min_samples_leaf
         self.max_features, self.n_bins, self.criterion, self.seed = max_features, n_bins, criterion, seed
         self.feature = torch.empty(0, dtype=torch.int64)
@@ -49,6 +97,8 @@ class DecisionTree(Writable):
     # ---------------------------------------------------------------- training
     def fit(self, X: torch.Tensor, y: torch.Tensor, sample_weight: Optional[torch.Tensor] = None,
             num_classes: Optional[int] = None, thresholds: Optional[torch.Tensor] = None) -> "DecisionTree":
+        if self.engine == "native":
+            return self._fit_native(X, y, sample_weight, num_classes, thresholds)
         dev = X.device
         n, d = X.shape
         w = torch.ones(n, dtype=torch.float64, device=dev) if sample_weight is None else sample_weight.double().to(dev)
@@ -138,6 +188,43 @@ class DecisionTree(Writable):
             self.value = (V[:, 1] / V[:, 0].clamp_min(1e-300))[:, None]
         return self
 
+    def _fit_native(self, X, y, sample_weight, num_classes, thresholds) -> "DecisionTree":
+        """One tree through ``ops.forest.grow``. Statistics kind: classification without
+        weights or with integer weights (<= 255) -> exact integer counts; real weights and
+        regression -> fp64 sums."""
+        dev = X.device
+        n, d = X.shape
+        cls = self.task == "classification"
+        C = int(num_classes or int(y.max()) + 1) if cls else 3
+        th = thresholds if thresholds is not None else _bins(X, self.n_bins)
+        B = th.shape[1] + 1
+        F.check_shape(B, C)
+        w = None if sample_weight is None else sample_weight.to(dev)
+        integer = w is None or bool(((w == w.round()) & (w >= 0) & (w <= 255)).all())
+        if integer and w is not None and float(w.sum()) >= 2.0 ** 32:
+            integer = False
+        mult = torch.ones((1, n), dtype=torch.uint8, device=dev)
+        yi = stats = None
+        if cls and integer:
+            kind = F.COUNT
+            yi = y.to(dev).int()
+            if w is not None:
+                mult = w.to(torch.uint8).reshape(1, n)
+        else:
+            kind = F.REAL
+            wd = torch.ones(n, dtype=torch.float64, device=dev) if w is None else w.double()
+            if cls:
+                stats = torch.nn.functional.one_hot(y.long().to(dev), C).double() * wd[:, None]
+            else:
+                yd = y.double().to(dev).reshape(n)
+                stats = torch.stack([wd, wd * yd, wd * yd * yd], 1)
+        packed = F.grow(F.bin_features(X, th), d, B, C, kind, mult, task=F.task_id(self.task, self.criterion),
+                        max_depth=self.max_depth, min_leaf=self.min_leaf, k_sub=_n_sub(self.max_features, d),
+                        seed=self.seed, y=yi, stats=stats)
+        t = _trees_from_packed(packed, th, self, [self.seed])[0]
+        self.feature, self.threshold, self.left, self.value = t.feature, t.threshold, t.left, t.value
+        return self
+
     def _count(self, S):
         return S.sum(-1) if self.task == "classification" else S[..., 0]
 
@@ -209,38 +296,123 @@ class DecisionTree(Writable):
 class DecisionForest:
     """Random forest: bootstrap rows + sqrt(d) features per split. ``fit_distributed``
     trains ``n_trees / P`` trees per worker on its local rows and all-gathers the trees
-    (the contrib RF combines per-mapper trees the same way)."""
+    (the contrib RF combines per-mapper trees the same way); with ``engine="native"`` and
+    ``mode="rows"`` it trains ONE forest over the workers' row shards instead (Poisson(1)
+    bootstrap keyed by the global row index, one histogram all-reduce per level)."""
 
     def __init__(self, task="classification", n_trees=50, max_depth=10, max_features="sqrt", n_bins=64, seed=0,
-                 min_samples_leaf=1):
+                 min_samples_leaf=1, engine="torch", criterion="gini"):
+        if engine not in ENGINES:
+            raise ValueError(f"engine must be one of {ENGINES} (got {engine!r})")
+        self.engine, self.criterion = engine, criterion
+        self._pack = None
         self.task, self.n_trees, self.max_depth = task, n_trees, max_depth
         self.max_features, self.n_bins, self.seed, self.min_leaf = max_features, n_bins, seed, min_samples_leaf
         self.trees: List[DecisionTree] = []
         self.num_classes = None
 
-    def fit(self, X, y, num_classes=None, n_trees=None, seed_offset=0):
+    def fit(self, X, y, num_classes=None, n_trees=None, seed_offset=0, thresholds=None):
         n = X.shape[0]
         self.num_classes = num_classes or (int(y.max()) + 1 if self.task == "classification" else None)
-        th = _bins(X, self.n_bins)
+        th = thresholds if thresholds is not None else _bins(X, self.n_bins)
+        if self.engine == "native":
+            return self._fit_native(X, y, th, n_trees or self.n_trees, self.seed + seed_offset)
         g = torch.Generator().manual_seed(self.seed + seed_offset)
         for t in range(n_trees or self.n_trees):
             idx = torch.randint(0, n, (n,), generator=g).to(X.device)
             w = torch.bincount(idx, minlength=n).double()
             tree = DecisionTree(self.task, self.max_depth, self.min_leaf, self.max_features, self.n_bins,
-                                seed=self.seed * 1000 + seed_offset + t)
+                                self.criterion, seed=self.seed * 1000 + seed_offset + t)
             self.trees.append(tree.fit(X, y, sample_weight=w, num_classes=self.num_classes, thresholds=th))
         return self
 
-    def fit_distributed(self, X, y, comm: Communicator, num_classes=None):
+    def _fit_native(self, X, y, th, n_trees, seed, row0=0, reduce=None, n_total=None):
+        """Train ``n_trees`` trees in batches through ``ops.forest.grow`` and append them.
+        ``n_total``: rows over all shards (the batch size must not depend on the shard)."""
+        dev = X.device
+        n, d = X.shape
+        cls = self.task == "classification"
+        C = int(self.num_classes) if cls else 3
+        B = th.shape[1] + 1
+        F.check_shape(B, C)
+        Xb = F.bin_features(X, th)
+        yi = stats = None
+        if cls:
+            kind, yi = F.COUNT, y.to(dev).int()
+        else:
+            kind = F.REAL
+            yd = y.double().to(dev).reshape(n)
+            stats = torch.stack([torch.ones_like(yd), yd, yd * yd], 1)
+        proto = DecisionTree(self.task, self.max_depth, self.min_leaf, self.max_features, self.n_bins,
+                             self.criterion, engine="native")
+        step = F.trees_per_batch(n_total or n, d, B, C, kind, self.max_depth)
+        for t0 in range(0, n_trees, step):
+            tb = min(step, n_trees - t0)
+            mult = F.bootstrap(seed, t0, tb, row0, n, dev)
+            packed = F.grow(Xb, d, B, C, kind, mult, task=F.task_id(self.task, self.criterion),
+                            max_depth=self.max_depth,
+                            min_leaf=self.min_leaf, k_sub=_n_sub(self.max_features, d), seed=seed, tree0=t0, y=yi,
+                            stats=stats, reduce=reduce)
+            self.trees += _trees_from_packed(packed, th, proto, [seed * 1000 + t0 + i for i in range(tb)])
+        self._pack = None
+        return self
+
+    def _fit_rows(self, X, y, comm: Communicator, num_classes, thresholds):
+        """Data-parallel fit: every worker holds a row shard and ends with the same forest."""
+        if self.engine != "native":
+            raise ValueError('fit_distributed(mode="rows") needs engine="native"')
+        sizes = comm.all_gather_ints([X.shape[0]])[:, 0].tolist()
+        row0 = sum(sizes[:comm.rank])
+        if self.task == "classification":
+            if num_classes is None:
+                top = torch.tensor([int(y.max()) if y.numel() else 0], dtype=torch.int64, device=comm.device)
+                comm.all_reduce(top, op=torch.distributed.ReduceOp.MAX)
+                num_classes = int(top) + 1
+            self.num_classes = int(num_classes)
+        th = thresholds
+        if th is None:  # rank 0's quantiles for everyone
+            th = _bins(X, self.n_bins) if comm.rank == 0 else torch.empty((X.shape[1], self.n_bins - 1),
+                                                                          dtype=torch.float64, device=X.device)
+            th = th.contiguous()
+            comm.broadcast(th, 0)
+        return self._fit_native(X, y, th.to(X.device), self.n_trees, self.seed, row0=row0,
+                                reduce=lambda H: comm.all_reduce(H), n_total=sum(sizes))
+
+    def fit_distributed(self, X, y, comm: Communicator, num_classes=None, mode="trees", thresholds=None):
+        """``mode="trees"``: whole trees per worker on its local rows, all-gathered.
+        ``mode="rows"`` (native engine): one forest over the workers' row shards."""
         from ..parallel.partition_util import allgather_objects
 
+        if mode == "rows":
+            return self._fit_rows(X, y, comm, num_classes, thresholds)
+        if mode != "trees":
+            raise ValueError(f'mode must be "trees" or "rows" (got {mode!r})')
         P, r = comm.world_size, comm.rank
         mine = self.n_trees // P + (1 if r < self.n_trees % P else 0)
         self.fit(X, y, num_classes, n_trees=mine, seed_offset=7919 * r)
         self.trees = allgather_objects(comm, self.trees)
+        self._pack = None
         return self
 
+    def _packed(self, device):
+        """The forest's arrays concatenated on ``device`` (built once per forest and device)."""
+        key = (str(device), len(self.trees))
+        if self._pack is None or self._pack[0] != key:
+            self._pack = (key, F.pack_trees(self.trees, device))
+        return self._pack[1]
+
+    def _use_kernel(self, X) -> bool:
+        return self.engine == "native" and X.device.type == "cuda" and len(self.trees) > 0
+
+    def apply(self, X):
+        """Leaf index of every sample in every tree, [n_trees, n]."""
+        if self._use_kernel(X):
+            return F.predict_packed(X, self._packed(X.device), proba=False, leaves=True)[1]
+        return torch.stack([t.apply(X) for t in self.trees])
+
     def predict_proba(self, X):
+        if self._use_kernel(X):
+            return F.predict_packed(X, self._packed(X.device))[0]
         return torch.stack([t.predict_proba(X) for t in self.trees]).mean(0)
 
     def predict(self, X):
