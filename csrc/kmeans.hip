@@ -75,7 +75,7 @@ __device__ __forceinline__ void stage_dma(const __bf16* __restrict__ cm2, int ti
   }
 }
 
-template <int KS, int G, int WAVES, int RG, int PIPE, int PRIO = 0>
+template <int KS, int G, int WAVES, int RG, int PIPE, int PRIO = 0, int KEYLESS = 0>
 __global__ __launch_bounds__(WAVES * 64) void kmeans_assign_kernel(
     const __bf16* __restrict__ X, long ldx, const __bf16* __restrict__ Cm2, long N, int ntiles, int tail_rg,
     int dcount, int* __restrict__ labels, float* __restrict__ sums, int ld_sums, float* __restrict__ obj_partial,
@@ -112,10 +112,20 @@ __global__ __launch_bounds__(WAVES * 64) void kmeans_assign_kernel(
   // argmin of one 32x32 tile into (best, bestt)[g]: the 16 candidates' register index rides
   // in the low mantissa bits (one v_and_or per candidate). A plain v_min3 with the index
   // searched only on improvement measured 5 % slower (it spills; profiles/r2_ktail).
+  // KEYLESS (variant 16): the plain minimum of the 16 candidates, no index bits. The sweep then
+  // knows only the winning 32-row group; the row inside it is found by the gather-sum pass,
+  // which re-computes that one group's 32 distances per point (kmeans_resolve.hip).
   auto tile_argmin = [&](const floatx16& ac, int g, int tg) {
-    float m = keyed(ac[0], 0u);
+    float m;
+    if constexpr (KEYLESS) {
+      m = ac[0];
 #pragma unroll
-    for (int q = 1; q < 16; ++q) m = fminf(m, keyed(ac[q], (unsigned)q));
+      for (int q = 1; q < 16; ++q) m = fminf(m, ac[q]);
+    } else {
+      m = keyed(ac[0], 0u);
+#pragma unroll
+      for (int q = 1; q < 16; ++q) m = fminf(m, keyed(ac[q], (unsigned)q));
+    }
     if (m < best[g]) { best[g] = m; bestt[g] = tg; }
   };
 
@@ -233,12 +243,15 @@ __global__ __launch_bounds__(WAVES * 64) void kmeans_assign_kernel(
     xs -= (float)KM_ONES;  // the 1.0 columns of X
     const float ob = __shfl_xor(best[g], 32, 64);
     const int obt = __shfl_xor(bestt[g], 32, 64);
-    const bool take = h ? (ob <= best[g]) : (ob < best[g]);
+    // keyless: the smaller value, on equality the lower group (both halves agree)
+    const bool take = KEYLESS ? (ob < best[g] || (ob == best[g] && obt < bestt[g]))
+                              : (h ? (ob <= best[g]) : (ob < best[g]));
     const float bv = take ? ob : best[g];
     const int bt = take ? obt : bestt[g];
     const int hw = take ? (1 - h) : h;
     const unsigned reg = __float_as_uint(bv) & 0xFu;
-    const int idx = bt * 32 + (int)(reg & 3u) + 8 * (int)(reg >> 2) + 4 * hw;
+    // keyless: labels[p] is the winning 32-row group id, 0 .. swept_k / 32 - 1
+    const int idx = KEYLESS ? bt : bt * 32 + (int)(reg & 3u) + 8 * (int)(reg >> 2) + 4 * hw;
     lab[g] = idx;
     const long p = pbase + g * 32 + r;
     if (h == 0 && p < N) {
@@ -261,7 +274,7 @@ __global__ __launch_bounds__(WAVES * 64) void kmeans_assign_kernel(
   }
 
   // ---- accumulate (x, 1) rows into the per-centroid partial sums
-  if (sums) {
+  if (!KEYLESS && sums) {
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       for (int i = 0; i < 32; ++i) {
@@ -894,14 +907,14 @@ __global__ __launch_bounds__(256) void kmeans_wide_finish_kernel(const unsigned 
   if (threadIdx.x == 0 && obj_partial) obj_partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-template <int KS, int G, int WAVES, int RG, int PIPE = 0, int PRIO = 0>
+template <int KS, int G, int WAVES, int RG, int PIPE = 0, int PRIO = 0, int KEYLESS = 0>
 int launch_assign(const void* X, long ldx, const void* Cm2, long N, int Kp, int d, int* labels, float* sums,
                   int ld_sums, float* obj_partial, float* mind, hipStream_t stream) {
   using C = KMCfg<KS, G, WAVES, RG>;
-  if (Kp % 32) return HARP_EBADARG;
+  if (Kp % 32 || (KEYLESS && sums)) return HARP_EBADARG;  // no fused atomics in the keyless sweep
   const long nblk = (N + C::PTS - 1) / C::PTS;
   const int ntiles = (Kp + C::TILE - 1) / C::TILE, tail_rg = (Kp % C::TILE) / 32;
-  kmeans_assign_kernel<KS, G, WAVES, RG, PIPE, PRIO><<<dim3((unsigned)nblk), dim3(C::THREADS), 0, stream>>>(
+  kmeans_assign_kernel<KS, G, WAVES, RG, PIPE, PRIO, KEYLESS><<<dim3((unsigned)nblk), dim3(C::THREADS), 0, stream>>>(
       (const __bf16*)X, ldx, (const __bf16*)Cm2, N, ntiles, tail_rg, d, labels, sums, ld_sums, obj_partial, mind);
   return harp_launch_status();
 }
@@ -910,13 +923,17 @@ int launch_assign(const void* X, long ldx, const void* Cm2, long N, int Kp, int 
 // hold round_up(Kp, 128) rows (the last stage's DMA reads the whole tile).
 // Only the measured frontier ships (profiles/r1_kmeans_*): 15 (= 14 + static priority for the
 // younger half, profiles/r3_setprio) is the default for d <= 124, 13 the RG=2 neighbour of 14,
-// 4 the one-group shape wide rows (9..16 k-steps) use.
+// 4 the one-group shape wide rows (9..16 k-steps) use. 16 is 15 without index keys: it writes
+// the winning 32-row group id (0 .. Kp / 32 - 1) to labels and takes no fused sums; the
+// caller finishes the labels with harp_kmeans_resolve_rowsum (kmeans_resolve.hip). The
+// default for rows of <= 128 padded columns with bucketed sums (profiles/r7_keyless).
 #define KM_VARIANTS(KS)                                                                       \
   switch (variant) {                                                                        \
     case 4: return launch_assign<KS, 1, 16, 2>(X, ldx, Cm2, N, Kp, d, labels, sums, ld, op, md, s);  \
     case 13: return launch_assign<KS, 4, 8, 2, 2>(X, ldx, Cm2, N, Kp, d, labels, sums, ld, op, md, s); \
     case 14: return launch_assign<KS, 4, 8, 4, 2>(X, ldx, Cm2, N, Kp, d, labels, sums, ld, op, md, s); \
     case 15: return launch_assign<KS, 4, 8, 4, 2, 1>(X, ldx, Cm2, N, Kp, d, labels, sums, ld, op, md, s); \
+    case 16: return launch_assign<KS, 4, 8, 4, 2, 1, 1>(X, ldx, Cm2, N, Kp, d, labels, sums, ld, op, md, s); \
     default: return HARP_EBADARG;                                                           \
   }
 
@@ -925,7 +942,7 @@ int launch_assign(const void* X, long ldx, const void* Cm2, long N, int Kp, int 
 HARP_EXPORT int harp_kmeans_points_per_block(int variant) {
   switch (variant) {
     case 4: return 16 * 1 * 32;
-    case 13: case 14: case 15: return 8 * 4 * 32;
+    case 13: case 14: case 15: case 16: return 8 * 4 * 32;
     default: return -1;
   }
 }

@@ -29,8 +29,20 @@ from . import _lib
 KP_ALIGN = 128
 ONES = 4  # X columns d..d+3 hold 1.0
 # (G4, W8, RG4, pipelined; 1024 points per workgroup) with static VALU priority for waves 4-7
-# (15; 14 without it: 0.2 % slower, profiles/r3_setprio)
-DEFAULT_VARIANT = 15
+# (15; 14 without it: 0.2 % slower, profiles/r3_setprio). 16 is the keyless form of 15: the
+# sweep finds only the winning 32-row centroid group (no index bits in the distances: 2.0
+# instead of 4.3 VALU instructions per MFMA) and the bucketed gather-sum pass, which reads
+# every row anyway, finds the row inside the group (csrc/kmeans_resolve.hip;
+# profiles/r7_keyless). Calls without a bucketed sum to resolve in run 15.
+DEFAULT_VARIANT = 16
+KEYLESS_VARIANT, KEYED_VARIANT = 16, 15
+KEYLESS_MAX_DP = 128
+# The resolve pass scatters one 4-byte label per point. Run over all 1e8 points at once, the
+# label lines being written span 400 MB and every store goes to HBM as a partial line
+# (bucket + resolve 9.2 ms); over spans of points whose labels fit the memory-side cache the
+# stores merge there (7.55 ms at 4 or 16 spans; 64 spans pay launch gaps, 9.9 ms;
+# profiles/r7_keyless). Smaller inputs run as one span.
+RESOLVE_SPAN = 1 << 23
 
 
 NARROW_MAX_DP = 256  # the register-resident assign kernel (X fragments live for the sweep)
@@ -179,6 +191,9 @@ def assign(X: torch.Tensor, op: CentroidOperand, sums: Optional[torch.Tensor] = 
     deterministic) or "atomic" (fused fp32 atomics in the assign kernel).
     ``min_dist`` (fp32 [n], optional) receives each point's squared distance to its
     centroid (used to merge partial argmins across centroid blocks under rotation).
+    ``variant`` 16 (the default) is keyless: with bucketed sums and rows of at most 128 padded
+    columns the sweep finds the 32-row centroid group and the gather-sum pass the row inside
+    it; ties go to the lowest index, as ``torch.argmin`` does. Callers always get final labels.
     Returns (labels, objective)."""
     n, dp = X.shape
     dev = X.device
@@ -191,6 +206,12 @@ def assign(X: torch.Tensor, op: CentroidOperand, sums: Optional[torch.Tensor] = 
                 raise ValueError("accumulate='atomic' is only fused into the narrow kernel (dp <= "
                                  f"{NARROW_MAX_DP}); the wide path (dp = {dp}) accumulates by bucket")
             return _assign_wide(X, op, sums, labels, want_objective, obj_partial, min_dist)
+        # the keyless sweep needs the bucketed gather-sum to finish its labels; every other
+        # call (no sums, min_dist, fused atomics, wide rows) runs the keyed kernel
+        keyless = (variant == KEYLESS_VARIANT and dp <= KEYLESS_MAX_DP and sums is not None
+                   and accumulate == "bucket" and min_dist is None)
+        if variant == KEYLESS_VARIANT and not keyless:
+            variant = KEYED_VARIANT
         if dp > 128:
             variant = 4  # the only instantiation for 9..16 k-steps
         elif variant in (14, 15) and dp // 16 == 5:
@@ -229,16 +250,24 @@ def assign(X: torch.Tensor, op: CentroidOperand, sums: Optional[torch.Tensor] = 
                 continue
             from . import segment
 
+            def bucket_sum(lab, Xc):
+                if keyless:  # lab holds 32-row group ids: sort by group, resolve the row, sum
+                    for s0 in range(0, lab.numel(), RESOLVE_SPAN):
+                        ls, Xs = lab[s0:s0 + RESOLVE_SPAN], Xc[s0:s0 + RESOLVE_SPAN]
+                        perm, start = segment.bucket_labels(ls, swept_k(op) // 32)
+                        segment.resolve_rowsum(Xs, op.Cm2, perm, start, ls, sums)
+                else:
+                    perm, start = segment.bucket_labels(lab, op.Cm2.shape[0])
+                    segment.bucket_rowsum(Xc, perm, start, sums)
+
             if side is None:
-                perm, start = segment.bucket_labels(labels, op.Cm2.shape[0])
-                segment.bucket_rowsum(X, perm, start, sums)
+                bucket_sum(labels, X)
                 continue
             # bucket + gather-sum of this chunk on the side stream while the next chunk's
             # assign runs: the memory-bound row sums fill the gaps of the MFMA-bound assign
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                perm, start = segment.bucket_labels(labels[r0:r1], op.Cm2.shape[0])
-                segment.bucket_rowsum(X[r0:r1], perm, start, sums)
+                bucket_sum(labels[r0:r1], X[r0:r1])
         if side is not None:
             main.wait_stream(side)
         obj = obj_partial[:nblk].double().sum() if want_objective else None

@@ -21,6 +21,10 @@ _lib.register({
                            _lib.c_void_p],
     "harp_bucket_rowsum_bf16": [_lib.c_void_p, _lib.c_int, _lib.c_long, _lib.c_void_p, _lib.c_void_p, _lib.c_int,
                                 _lib.c_long, _lib.c_void_p, _lib.c_int, _lib.c_void_p],
+    # X, ldx, Cm2, dp, perm, start, NG, n, labels, sums, ld, stream
+    "harp_kmeans_resolve_rowsum": [_lib.c_void_p, _lib.c_long, _lib.c_void_p, _lib.c_int, _lib.c_void_p,
+                                   _lib.c_void_p, _lib.c_int, _lib.c_long, _lib.c_void_p, _lib.c_void_p, _lib.c_int,
+                                   _lib.c_void_p],
 })
 _WS: Dict[Tuple, torch.Tensor] = {}
 
@@ -44,6 +48,11 @@ def bucket_labels(labels: torch.Tensor, K: int) -> Tuple[torch.Tensor, torch.Ten
     stream = torch.cuda.current_stream(labels.device).cuda_stream
     key = (labels.device, n, K, stream)
     ws = _WS.get(key)
+    if ws is None:
+        # a larger workspace already alive on this stream serves a smaller call (the spans of
+        # one K-means pass, ops.kmeans.RESOLVE_SPAN: the last one is shorter)
+        ws = next((w for k, w in _WS.items() if k[0] == labels.device and k[3] == stream and w.numel() >= need),
+                  None)
     if ws is None:
         for k in [k for k in _WS if k[3] == stream]:
             del _WS[k]  # one workspace alive per stream (allocated and reused on that stream)
@@ -76,4 +85,23 @@ def bucket_rowsum(X: torch.Tensor, perm: torch.Tensor, start: torch.Tensor, out:
                                                     start.data_ptr(), K, perm.numel(), out[:, c0:].data_ptr(),
                                                     out.stride(0), _lib.stream_ptr(X.device))
         _lib.check(st, "bucket_rowsum")
+    return out
+
+
+def resolve_rowsum(X: torch.Tensor, Cm2: torch.Tensor, perm: torch.Tensor, start: torch.Tensor,
+                   labels: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """Second half of the keyless K-means assign (csrc/kmeans_resolve.hip): ``perm`` / ``start``
+    bucket the points by winning 32-row centroid group; one pass over the sorted rows writes
+    the final ``labels[p] = 32 * group + argmin row`` and adds every row into ``out[label]``
+    (zero ``out`` first for a plain sum). GPU only, rows of at most 128 columns."""
+    NG = start.numel() - 1
+    dp = X.shape[1]
+    assert X.dtype == torch.bfloat16 and X.stride(1) == 1 and out.dtype == torch.float32 and out.is_contiguous()
+    assert Cm2.dtype == torch.bfloat16 and Cm2.is_contiguous() and Cm2.shape[1] == dp and Cm2.shape[0] >= 32 * NG
+    assert out.shape[0] >= 32 * NG and labels.dtype == torch.int32 and labels.is_contiguous()
+    assert labels.numel() == perm.numel() == X.shape[0]
+    st = _lib.kernels().harp_kmeans_resolve_rowsum(X.data_ptr(), X.stride(0), Cm2.data_ptr(), dp, perm.data_ptr(),
+                                                   start.data_ptr(), NG, perm.numel(), labels.data_ptr(),
+                                                   out.data_ptr(), out.stride(0), _lib.stream_ptr(X.device))
+    _lib.check(st, "kmeans_resolve_rowsum")
     return out

@@ -20,6 +20,9 @@ def main():
     ap.add_argument("--d", type=int, default=100)
     ap.add_argument("--variant", type=int, default=K.DEFAULT_VARIANT)
     ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--sums", action="store_true",
+                    help="with the bucketed (x, count) sums: the path the keyless variant 16 needs "
+                         "(without them it runs the keyed kernel 15)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     n = int(a.n)
@@ -27,8 +30,11 @@ def main():
     c = torch.rand(a.k, a.d, device=dev) * 1000
     op = K.prepare(c, X.shape[1])
     lab = torch.empty(n, dtype=torch.int32, device=dev)
+    sums = torch.zeros((K.padded_k(a.k), X.shape[1]), dtype=torch.float32, device=dev) if a.sums else None
     for _ in range(a.reps):
-        K.assign(X, op, labels=lab, want_objective=False, variant=a.variant)
+        if sums is not None:
+            sums.zero_()
+        K.assign(X, op, sums=sums, labels=lab, want_objective=False, variant=a.variant)
     torch.cuda.synchronize()
     print("ok", a.variant)
 
