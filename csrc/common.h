@@ -26,8 +26,6 @@ static inline int harp_launch_status() {
   return e == hipSuccess ? HARP_OK : HARP_ELAUNCH;
 }
 
-__device__ __forceinline__ float bf16_to_f32(__bf16 v) { return (float)v; }
-
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

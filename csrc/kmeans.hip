@@ -226,7 +226,8 @@ __global__ __launch_bounds__(WAVES * 64) void kmeans_assign_kernel(
     }
   }
 
-  // ---- resolve argmin across the two lane halves, write labels / objective partials
+  // ---- resolve argmin across the two lane halves, write labels / objective partials (the
+  // keyed half exchange and the row decode stand in both wide kernels too: change all three)
   int lab[G];
   float local_obj = 0.f;
 #pragma unroll
@@ -363,30 +364,59 @@ __global__ void uniform_rows_bf16_kernel(__bf16* __restrict__ X, long N, int d, 
 // ---------------------------------------------------------------------------------------
 // Wide rows (dp > 256, any d up to the operand's padding): X fragments no longer fit the
 // register file for a whole centroid sweep, so the reduction over features is staged:
-//  * a workgroup (4 waves, 64 points per wave = 2 MFMA point groups) owns 256 points and ONE
-//    block of 256 centroids (8 row groups of 32); its 16 accumulators (256 fp32 per lane)
-//    stay live across the feature stages;
+//  * a workgroup owns 256 points (4 wave columns of G MFMA point groups of 32) and ONE block
+//    of 256 centroids (8 row groups of 32); its accumulators stay live across the feature
+//    stages (16 per wave at 4 waves; 8 at 8 waves, where each wave column is two waves with
+//    half the row groups each);
 //  * feature stage f covers dp columns [64 f, 64 f + 64): the centroid block's 256 x 64 bf16
-//    slice streams through double-buffered LDS by LDS-DMA (the swizzled image of the
-//    narrow kernel), the points' 64-column slices are register double-buffered straight
-//    from global (next stage's loads in flight under this stage's 64 MFMAs per wave);
-//  * the epilogue is the narrow kernel's keyed argmin over the block's 256 candidates, the
-//    workgroup's result (squared distance, index) is merged across centroid blocks with ONE
+//    slice streams through LDS by LDS-DMA (the swizzled image of the narrow kernel). The
+//    register kernel (variants 1, 3) double-buffers it and loads the points' 64-column
+//    slices straight from global into double-buffered registers (next stage's loads in
+//    flight under this stage's MFMAs); the ring kernel (variants 5, 6) sends the points'
+//    slice through LDS-DMA as well, both into one slot of an NBUF-deep ring;
+//  * the epilogue is the narrow kernel's keyed argmin over the wave's candidates, the
+//    result (squared distance, index) is merged across waves and centroid blocks with ONE
 //    64-bit atomic min per point (distance bits above the index: non-negative floats order
 //    as integers, ties go to the lower index);
 //  * grid: consecutive ids of one XCD (id mod 8) take the centroid blocks of one point block
 //    one after another, so that block's rows come from HBM once and from L2 after.
 constexpr int KW_CB = 256, KW_RG = KW_CB / 32;  // centroids per workgroup (8 row groups of 32)
 
-// G point groups of 32 per wave (4 waves), DC features per stage, OCC waves per SIMD
+// G point groups of 32 per wave column (4 columns), DC features per stage
 template <int G, int DC>
 struct KWCfg {
   static constexpr int KS = DC / 16;                  // MFMA k-steps per stage
-  static constexpr int CPR = DC / 8;                  // 16-B chunks per centroid row per stage
-  static constexpr int TILE_BYTES = KW_CB * DC * 2;
-  static constexpr int DMA = KW_CB * CPR / 64;        // 1-KiB DMA pieces per stage
+  static constexpr int CPR = DC / 8;                  // 16-B chunks per row per stage
+  static constexpr int TILE_BYTES = KW_CB * DC * 2;   // centroid slice per stage
+  static constexpr int DMA = KW_CB * CPR / 64;        // its 1-KiB DMA pieces
   static constexpr int PTS = 4 * G * 32;              // points per workgroup
+  static constexpr int XBYTES = PTS * DC * 2;         // point slice per stage (ring kernel)
+  static constexpr int XDMA = PTS * CPR / 64;         // its 1-KiB DMA pieces
 };
+
+// XCD-aware blockIdx -> (point block pb, centroid block kb): ids x, x + 8, x + 16, ... (one
+// XCD) walk the nkb centroid blocks of one point block before the next. valid is false for
+// the ids of a last round of 8 that name no point block: those workgroups return at once.
+// row0() is the block's first centroid row, live_blk() its row groups below kswept; they are
+// derived after that return (computed in front of it, the kernels' code changes).
+struct KWBlock {
+  long pb;
+  int kb;
+  bool valid;
+  __device__ int row0() const { return kb * KW_CB; }
+  __device__ int live_blk(int kswept) const {
+    return (kswept - row0()) >= KW_CB ? KW_RG : (kswept - row0() + 31) / 32;
+  }
+};
+template <int PTS>
+__device__ __forceinline__ KWBlock wide_block(long N, int nkb) {
+  const long id = blockIdx.x;
+  const long xcd = id & 7, round = id >> 3;
+  const long pb = (round / nkb) * 8 + xcd;
+  const int kb = (int)(round % nkb);
+  const long npb = (N + PTS - 1) / PTS;
+  return {pb, kb, pb < npb};
+}
 
 // LDS chunk rotation of centroid row `row` for the wide tiles: ds_read_b128 serves 16 lanes
 // (rows r..r+15 of one 16-B chunk column) per LDS cycle, so their 16 addresses must fall on
@@ -398,11 +428,13 @@ __device__ __forceinline__ int wide_rot(int row) {
   return CPR == 4 ? (row >> 2) & 3 : CPR == 8 ? (row >> 1) & 7 : CPR == 16 ? row & 15 : (row >> 3) & 1;
 }
 
-template <class C>
+// stage f of the centroid block at row0 -> its rotated LDS image, by all WAVES waves
+template <class C, int WAVES>
 __device__ __forceinline__ void stage_dma_wide(const __bf16* __restrict__ cm2, int dp, int row0, int kp, int f,
                                                char* lds, int wave, int lane) {
+  static_assert(C::DMA % WAVES == 0, "whole pieces per wave");
 #pragma unroll
-  for (int j0 = 0; j0 < C::DMA; j0 += 4) {
+  for (int j0 = 0; j0 < C::DMA; j0 += WAVES) {
     const int j = j0 + wave;
     const int q = j * 64 + lane;
     const int row = q / C::CPR;
@@ -416,6 +448,7 @@ __device__ __forceinline__ void stage_dma_wide(const __bf16* __restrict__ cm2, i
   }
 }
 
+// The register kernel: 4 waves, each all 8 row groups x G point groups; OCC waves per SIMD
 template <int G, int DC, int OCC>
 __global__ __launch_bounds__(256, OCC) void kmeans_assign_wide_kernel(
     const __bf16* __restrict__ X, long ldx, const __bf16* __restrict__ Cm2, long N, int dp, int kswept, int kp,
@@ -425,21 +458,13 @@ __global__ __launch_bounds__(256, OCC) void kmeans_assign_wide_kernel(
   __shared__ __attribute__((aligned(16))) char smem[2 * C::TILE_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
-  const int srot = (r >> 3) & 1;
-  // XCD-aware id -> (point block, centroid block): ids x, x + 8, x + 16, ... (one XCD) walk
-  // the nkb centroid blocks of one point block before the next
-  const long id = blockIdx.x;
-  const long xcd = id & 7, round = id >> 3;
-  const long pb = (round / nkb) * 8 + xcd;
-  const int kb = (int)(round % nkb);
-  const long npb = (N + C::PTS - 1) / C::PTS;
-  if (pb >= npb) return;
-  const int row0 = kb * KW_CB;
-  const int live_rg = (kswept - row0) >= KW_CB ? KW_RG : (kswept - row0 + 31) / 32;
-  const long pbase = pb * C::PTS + wave * (G * 32);
+  const KWBlock b = wide_block<C::PTS>(N, nkb);
+  if (!b.valid) return;
+  const int row0 = b.row0(), live_rg = b.live_blk(kswept);
+  const long pbase = b.pb * C::PTS + wave * (G * 32);
   const int nst = dp / DC;
 
-  stage_dma_wide<C>(Cm2, dp, row0, kp, 0, smem, wave, lane);
+  stage_dma_wide<C, 4>(Cm2, dp, row0, kp, 0, smem, wave, lane);
   const bf16x8* xrow[G];
 #pragma unroll
   for (int g = 0; g < G; ++g) {
@@ -472,7 +497,7 @@ __global__ __launch_bounds__(256, OCC) void kmeans_assign_wide_kernel(
   auto stage = [&](int f, auto curtag) {
     constexpr int cur = decltype(curtag)::value;
     if (f + 1 < nst) {
-      stage_dma_wide<C>(Cm2, dp, row0, kp, f + 1, smem + (cur ^ 1) * C::TILE_BYTES, wave, lane);
+      stage_dma_wide<C, 4>(Cm2, dp, row0, kp, f + 1, smem + (cur ^ 1) * C::TILE_BYTES, wave, lane);
 #pragma unroll
       for (int g = 0; g < G; ++g)
 #pragma unroll
@@ -517,6 +542,10 @@ __global__ __launch_bounds__(256, OCC) void kmeans_assign_wide_kernel(
     t += __shfl_xor(t, 32, 64);
     xsg[g] = t - (float)KM_ONES;
   }
+  // epilogue: keyed min over the live row groups, half exchange (the lower half wins equal
+  // keys), row decode, one 64-bit atomic min per point. The ring kernel below and the narrow
+  // kernel above hold the same lines: as a shared function they compile to other code in every
+  // kernel that calls it (profiles/r8_kwide_refactor), so a change goes into all three.
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     float best = KM_BIG;
@@ -549,199 +578,42 @@ __global__ __launch_bounds__(256, OCC) void kmeans_assign_wide_kernel(
   }
 }
 
-template <int G, int DC, int NBUF>
-__global__ __launch_bounds__(256, 1) void kmeans_assign_wide_lds_kernel(
+// The ring kernel: both operands through an NBUF-deep LDS-DMA ring. WAVES = 4: wave w takes
+// all 8 row groups x point column w (8 x G accumulators). WAVES = 8 (2 per SIMD) on the same
+// 256 x 256 tile: wave w takes centroid half w & 1 and point column w >> 1 (4 x G
+// accumulators), so each SIMD has a second wave to issue while one waits (the 4-wave form
+// parks 44 % of its cycles on instruction dependencies).
+template <int G, int DC, int NBUF, int WAVES>
+__global__ __launch_bounds__(WAVES * 64, 1) void kmeans_assign_wide_ring_kernel(
     const __bf16* __restrict__ X, long ldx, const __bf16* __restrict__ Cm2, long N, int dp, int kswept, int kp,
     int nkb, unsigned long long* __restrict__ keys) {
   using C = KWCfg<G, DC>;
   constexpr int KS = C::KS, CPR = C::CPR;
-  constexpr int XROWS = 4 * G * 32;                  // points per workgroup
-  constexpr int XBYTES = XROWS * DC * 2;             // point slice per stage
-  constexpr int SBYTES = C::TILE_BYTES + XBYTES;     // one ring slot
-  constexpr int XDMA = XROWS * CPR / 64;             // 1-KiB pieces of the point slice
-  constexpr int OPS = C::DMA / 4 + XDMA / 4;         // DMA instructions per wave per stage
-  static_assert(C::DMA % 4 == 0 && XDMA % 4 == 0, "whole pieces per wave");
+  constexpr int CW = WAVES / 4;                       // waves per point column, one centroid share each
+  constexpr int RGW = KW_RG / CW;                     // row groups per wave
+  constexpr int SBYTES = C::TILE_BYTES + C::XBYTES;   // one ring slot
+  constexpr int OPS = (C::DMA + C::XDMA) / WAVES;     // DMA instructions per wave per stage
+  static_assert(WAVES == 4 || WAVES == 8, "4 point columns x 1 or 2 centroid shares");
   __shared__ __attribute__((aligned(16))) char smem[NBUF * SBYTES];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
-  const long id = blockIdx.x;
-  const long xcd = id & 7, round = id >> 3;
-  const long pb = (round / nkb) * 8 + xcd;
-  const int kb = (int)(round % nkb);
-  const long npb = (N + XROWS - 1) / XROWS;
-  if (pb >= npb) return;
-  const int row0 = kb * KW_CB;
-  const int live_rg = (kswept - row0) >= KW_CB ? KW_RG : (kswept - row0 + 31) / 32;
-  const long p0 = pb * XROWS;  // first point of the workgroup
-  const long pbase = p0 + wave * (G * 32);
+  const int rgo = (wave % CW) * RGW;                  // first row group of this wave
+  const int pw = wave / CW;                           // point column of this wave
+  const KWBlock b = wide_block<C::PTS>(N, nkb);
+  if (!b.valid) return;
+  const int row0 = b.row0();
+  // this wave's share of the block's live row groups (one wave per column: all of them)
+  const int live_blk = b.live_blk(kswept);
+  const int live_rg = CW == 1 ? live_blk : (live_blk - rgo < 0 ? 0 : (live_blk - rgo > RGW ? RGW : live_blk - rgo));
+  const long p0 = b.pb * C::PTS;  // first point of the workgroup
+  const long pbase = p0 + pw * (G * 32);
   const int nst = dp / DC;
   auto issue = [&](int f, int slot) {
     char* buf = smem + slot * SBYTES;
-    stage_dma_wide<C>(Cm2, dp, row0, kp, f, buf, wave, lane);
+    stage_dma_wide<C, WAVES>(Cm2, dp, row0, kp, f, buf, wave, lane);
     char* xb = buf + C::TILE_BYTES;
 #pragma unroll
-    for (int j0 = 0; j0 < XDMA; j0 += 4) {
-      const int j = j0 + wave;
-      const int q = j * 64 + lane;
-      const int row = q / CPR;
-      int c = q - row * CPR - wide_rot<CPR>(row);
-      if (c < 0) c += CPR;
-      long pr = p0 + row;
-      if (pr > N - 1) pr = N - 1;
-      const __bf16* src = X + pr * ldx + f * DC + c * 8;
-      __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
-                                       (void __attribute__((address_space(3)))*)(xb + j * 1024), 16, 0, 0);
-    }
-  };
-  floatx16 acc[KW_RG][G];
-#pragma unroll
-  for (int a = 0; a < KW_RG; ++a)
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[a][g][q] = 0.f;
-  int aoff[KS];
-#pragma unroll
-  for (int k = 0; k < KS; ++k) aoff[k] = (r * CPR + (2 * k + h + wide_rot<CPR>(r)) % CPR) * 16;
-#pragma unroll
-  for (int q = 0; q < NBUF - 1; ++q)
-    if (q < nst) issue(q, q);
-  float xs[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) xs[g] = 0.f;
-  for (int f = 0; f < nst; ++f) {
-    // stage f landed when at most the younger stages' pieces are outstanding
-    const int younger = (nst - 1 - f) < (NBUF - 2) ? (nst - 1 - f) : (NBUF - 2);
-    if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * OPS) : "memory");
-    else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OPS) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (f + NBUF - 1 < nst) issue(f + NBUF - 1, (f + NBUF - 1) % NBUF);
-    const char* buf = smem + (f % NBUF) * SBYTES;
-    const char* xb = buf + C::TILE_BYTES + wave * (G * 32) * CPR * 16;
-    bf16x8 xf[G][KS];
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-      for (int k = 0; k < KS; ++k) xf[g][k] = *(const bf16x8*)(xb + g * 32 * CPR * 16 + aoff[k]);
-    // |x|^2 from the staged fragments (VALU work under the stage's MFMAs)
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-      for (int k = 0; k < KS; ++k)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xs[g] = fmaf((float)xf[g][k][j], (float)xf[g][k][j], xs[g]);
-    bf16x8 af[2][KS];
-#pragma unroll
-    for (int k = 0; k < KS; ++k) af[0][k] = *(const bf16x8*)(buf + aoff[k]);
-#pragma unroll
-    for (int rg = 0; rg < KW_RG; ++rg) {
-      if (rg + 1 < KW_RG) {
-        const char* nb = buf + (rg + 1) * 32 * CPR * 16;
-#pragma unroll
-        for (int k = 0; k < KS; ++k) af[(rg + 1) & 1][k] = *(const bf16x8*)(nb + aoff[k]);
-      }
-      if (rg < live_rg) {
-#pragma unroll
-        for (int g = 0; g < G; ++g)
-#pragma unroll
-          for (int k = 0; k < KS; ++k)
-            acc[rg][g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[rg & 1][k], xf[g][k], acc[rg][g], 0, 0, 0);
-      }
-    }
-  }
-  float xsg[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) xsg[g] = xs[g] + __shfl_xor(xs[g], 32, 64) - (float)KM_ONES;
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    float best = KM_BIG;
-    int bestt = 0;
-#pragma unroll
-    for (int rg = 0; rg < KW_RG; ++rg) {
-      if (rg >= live_rg) break;
-      float m = keyed(acc[rg][g][0], 0u);
-#pragma unroll
-      for (int q = 1; q < 16; ++q) m = fminf(m, keyed(acc[rg][g][q], (unsigned)q));
-      if (m < best) {
-        best = m;
-        bestt = rg;
-      }
-    }
-    const float ob = __shfl_xor(best, 32, 64);
-    const int obt = __shfl_xor(bestt, 32, 64);
-    const bool take = h ? (ob <= best) : (ob < best);
-    const float bv = take ? ob : best;
-    const int bt = take ? obt : bestt;
-    const int hw = take ? (1 - h) : h;
-    const unsigned reg = __float_as_uint(bv) & 0xFu;
-    const int idx = row0 + bt * 32 + (int)(reg & 3u) + 8 * (int)(reg >> 2) + 4 * hw;
-    const long p = pbase + g * 32 + r;
-    if (h == 0 && p < N) {
-      const float dist = fmaxf(bv + xsg[g], 0.f);
-      const unsigned long long key = ((unsigned long long)__float_as_uint(dist) << 32) | (unsigned)idx;
-      __hip_atomic_fetch_min(keys + p, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-
-// 8 waves (2 per SIMD) on the same 256 x 256 tile: wave w takes centroid half w & 1 and
-// point quarter w >> 1 (4 x 2 accumulators), so each SIMD has a second wave to issue while
-// one waits (the 4-wave form parks 44 % of its cycles on instruction dependencies)
-template <int C_DMA8, class C>
-__device__ __forceinline__ void stage_dma_wide8(const __bf16* __restrict__ cm2, int dp, int row0, int kp, int f,
-                                                char* lds, int wave, int lane) {
-#pragma unroll
-  for (int j0 = 0; j0 < C::DMA; j0 += 8) {
-    const int j = j0 + wave;
-    const int q = j * 64 + lane;
-    const int row = q / C::CPR;
-    int c = q - row * C::CPR - wide_rot<C::CPR>(row);
-    if (c < 0) c += C::CPR;
-    int gr = row0 + row;
-    if (gr > kp - 1) gr = kp - 1;
-    const __bf16* src = cm2 + (size_t)gr * dp + f * (C::CPR * 8) + c * 8;
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
-                                     (void __attribute__((address_space(3)))*)(lds + j * 1024), 16, 0, 0);
-  }
-}
-
-template <int G, int DC, int NBUF>
-__global__ __launch_bounds__(512, 1) void kmeans_assign_wide8_kernel(
-    const __bf16* __restrict__ X, long ldx, const __bf16* __restrict__ Cm2, long N, int dp, int kswept, int kp,
-    int nkb, unsigned long long* __restrict__ keys) {
-  using C = KWCfg<G, DC>;
-  constexpr int KS = C::KS, CPR = C::CPR;
-  constexpr int XROWS = 4 * G * 32;                  // points per workgroup (256 at G = 2)
-  constexpr int RGW = KW_RG / 2, GW = G;             // per wave: 4 centroid groups x G point groups
-  constexpr int XBYTES = XROWS * DC * 2;             // point slice per stage
-  constexpr int SBYTES = C::TILE_BYTES + XBYTES;     // one ring slot
-  constexpr int XDMA = XROWS * CPR / 64;             // 1-KiB pieces of the point slice
-  constexpr int OPS = C::DMA / 8 + XDMA / 8;         // DMA instructions per wave per stage
-  static_assert(C::DMA % 8 == 0 && XDMA % 8 == 0, "whole pieces per wave");
-  __shared__ __attribute__((aligned(16))) char smem[NBUF * SBYTES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int rgo = (wave & 1) * RGW;                  // first centroid group of this wave
-  const int pwo = (wave >> 1) * (GW * 32);           // first point of this wave in the block
-  const long id = blockIdx.x;
-  const long xcd = id & 7, round = id >> 3;
-  const long pb = (round / nkb) * 8 + xcd;
-  const int kb = (int)(round % nkb);
-  const long npb = (N + XROWS - 1) / XROWS;
-  if (pb >= npb) return;
-  const int row0 = kb * KW_CB;
-  const int live_blk = (kswept - row0) >= KW_CB ? KW_RG : (kswept - row0 + 31) / 32;
-  const int live_rg = live_blk - rgo < 0 ? 0 : (live_blk - rgo > RGW ? RGW : live_blk - rgo);
-  const long p0 = pb * XROWS;  // first point of the workgroup
-  const long pbase = p0 + pwo;
-  const int nst = dp / DC;
-  auto issue = [&](int f, int slot) {
-    char* buf = smem + slot * SBYTES;
-    stage_dma_wide8<0, C>(Cm2, dp, row0, kp, f, buf, wave, lane);
-    char* xb = buf + C::TILE_BYTES;
-#pragma unroll
-    for (int j0 = 0; j0 < XDMA; j0 += 8) {
+    for (int j0 = 0; j0 < C::XDMA; j0 += WAVES) {
       const int j = j0 + wave;
       const int q = j * 64 + lane;
       const int row = q / CPR;
@@ -779,7 +651,7 @@ __global__ __launch_bounds__(512, 1) void kmeans_assign_wide8_kernel(
     __syncthreads();
     if (f + NBUF - 1 < nst) issue(f + NBUF - 1, (f + NBUF - 1) % NBUF);
     const char* buf = smem + (f % NBUF) * SBYTES;
-    const char* xb = buf + C::TILE_BYTES + pwo * CPR * 16;
+    const char* xb = buf + C::TILE_BYTES + pw * (G * 32) * CPR * 16;
     const char* cb = buf + rgo * 32 * CPR * 16;
     bf16x8 xf[G][KS];
 #pragma unroll
@@ -815,6 +687,8 @@ __global__ __launch_bounds__(512, 1) void kmeans_assign_wide8_kernel(
   float xsg[G];
 #pragma unroll
   for (int g = 0; g < G; ++g) xsg[g] = xs[g] + __shfl_xor(xs[g], 32, 64) - (float)KM_ONES;
+  // epilogue: the register kernel's, over this wave's row groups rgo .. rgo + RGW - 1; with two
+  // waves per column a wave without a live row group posts no key
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     float best = KM_BIG;
@@ -839,7 +713,7 @@ __global__ __launch_bounds__(512, 1) void kmeans_assign_wide8_kernel(
     const unsigned reg = __float_as_uint(bv) & 0xFu;
     const int idx = row0 + (rgo + bt) * 32 + (int)(reg & 3u) + 8 * (int)(reg >> 2) + 4 * hw;
     const long p = pbase + g * 32 + r;
-    if (h == 0 && p < N && live_rg > 0) {
+    if (h == 0 && p < N && (CW == 1 || live_rg > 0)) {
       const float dist = fmaxf(bv + xsg[g], 0.f);
       const unsigned long long key = ((unsigned long long)__float_as_uint(dist) << 32) | (unsigned)idx;
       __hip_atomic_fetch_min(keys + p, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -847,44 +721,26 @@ __global__ __launch_bounds__(512, 1) void kmeans_assign_wide8_kernel(
   }
 }
 
-template <int G, int DC, int NBUF>
-int launch_wide8(const void* X, long ldx, const void* Cm2, long N, int dp, int kswept, int kp,
-                 unsigned long long* keys, hipStream_t s) {
-  constexpr int XROWS = 4 * G * 32;
-  if (dp % DC || (ldx * 2) % 16) return HARP_EBADARG;
-  const long npb = (N + XROWS - 1) / XROWS;
-  const int nkb = (kswept + KW_CB - 1) / KW_CB;
-  const long rounds = (npb + 7) / 8 * nkb;
-  kmeans_assign_wide8_kernel<G, DC, NBUF><<<dim3((unsigned)(rounds * 8)), dim3(512), 0, s>>>(
-      (const __bf16*)X, ldx, (const __bf16*)Cm2, N, dp, kswept, kp, nkb, keys);
-  return harp_launch_status();
-}
-
-template <int G, int DC, int NBUF>
-int launch_wide_lds(const void* X, long ldx, const void* Cm2, long N, int dp, int kswept, int kp,
-                    unsigned long long* keys, hipStream_t s) {
-  constexpr int XROWS = 4 * G * 32;
-  constexpr int SBYTES = KW_CB * DC * 2 + XROWS * DC * 2;
-  if (dp % DC || (ldx * 2) % 16) return HARP_EBADARG;
-  const long npb = (N + XROWS - 1) / XROWS;
-  const int nkb = (kswept + KW_CB - 1) / KW_CB;
-  const long rounds = (npb + 7) / 8 * nkb;
-  (void)SBYTES;
-  kmeans_assign_wide_lds_kernel<G, DC, NBUF><<<dim3((unsigned)(rounds * 8)), dim3(256), 0, s>>>(
-      (const __bf16*)X, ldx, (const __bf16*)Cm2, N, dp, kswept, kp, nkb, keys);
-  return harp_launch_status();
-}
-
+// a wide tiling's entry point with the shape it is launched at, named together so that the
+// two cannot be paired wrongly at the call
+struct WideTiling {
+  void (*kernel)(const __bf16*, long, const __bf16*, long, int, int, int, int, unsigned long long*);
+  int waves, pts, dc;  // waves and points per workgroup, features per stage
+};
 template <int G, int DC, int OCC>
-int launch_wide(const void* X, long ldx, const void* Cm2, long N, int dp, int kswept, int kp,
+constexpr WideTiling wide_reg{kmeans_assign_wide_kernel<G, DC, OCC>, 4, KWCfg<G, DC>::PTS, DC};
+template <int G, int DC, int NBUF, int WAVES>
+constexpr WideTiling wide_ring{kmeans_assign_wide_ring_kernel<G, DC, NBUF, WAVES>, WAVES, KWCfg<G, DC>::PTS, DC};
+
+// one launcher for every wide tiling
+int launch_wide(const WideTiling& t, const void* X, long ldx, const void* Cm2, long N, int dp, int kswept, int kp,
                 unsigned long long* keys, hipStream_t s) {
-  using C = KWCfg<G, DC>;
-  if (dp % DC) return HARP_EBADARG;
-  const long npb = (N + C::PTS - 1) / C::PTS;
+  if (dp % t.dc) return HARP_EBADARG;
+  const long npb = (N + t.pts - 1) / t.pts;
   const int nkb = (kswept + KW_CB - 1) / KW_CB;
   const long rounds = (npb + 7) / 8 * nkb;
-  kmeans_assign_wide_kernel<G, DC, OCC><<<dim3((unsigned)(rounds * 8)), dim3(256), 0, s>>>(
-      (const __bf16*)X, ldx, (const __bf16*)Cm2, N, dp, kswept, kp, nkb, keys);
+  t.kernel<<<dim3((unsigned)(rounds * 8)), dim3(t.waves * 64), 0, s>>>((const __bf16*)X, ldx, (const __bf16*)Cm2, N,
+                                                                      dp, kswept, kp, nkb, keys);
   return harp_launch_status();
 }
 
@@ -919,7 +775,8 @@ int launch_assign(const void* X, long ldx, const void* Cm2, long N, int Kp, int 
   return harp_launch_status();
 }
 
-// variant -> (G, WAVES, RG, PIPE). Kp (the rows swept) must be a multiple of 32; Cm2 must
+// variant -> (G, WAVES, RG, PIPE, PRIO, KEYLESS), the one table both the launch and
+// harp_kmeans_points_per_block read. Kp (the rows swept) must be a multiple of 32; Cm2 must
 // hold round_up(Kp, 128) rows (the last stage's DMA reads the whole tile).
 // Only the measured frontier ships (profiles/r1_kmeans_*): 15 (= 14 + static priority for the
 // younger half, profiles/r3_setprio) is the default for d <= 124, 13 the RG=2 neighbour of 14,
@@ -927,22 +784,27 @@ int launch_assign(const void* X, long ldx, const void* Cm2, long N, int Kp, int 
 // the winning 32-row group id (0 .. Kp / 32 - 1) to labels and takes no fused sums; the
 // caller finishes the labels with harp_kmeans_resolve_rowsum (kmeans_resolve.hip). The
 // default for rows of <= 128 padded columns with bucketed sums (profiles/r7_keyless).
-#define KM_VARIANTS(KS)                                                                       \
-  switch (variant) {                                                                        \
-    case 4: return launch_assign<KS, 1, 16, 2>(X, ldx, Cm2, N, Kp, d, labels, sums, ld, op, md, s);  \
-    case 13: return launch_assign<KS, 4, 8, 2, 2>(X, ldx, Cm2, N, Kp, d, labels, sums, ld, op, md, s); \
-    case 14: return launch_assign<KS, 4, 8, 4, 2>(X, ldx, Cm2, N, Kp, d, labels, sums, ld, op, md, s); \
-    case 15: return launch_assign<KS, 4, 8, 4, 2, 1>(X, ldx, Cm2, N, Kp, d, labels, sums, ld, op, md, s); \
-    case 16: return launch_assign<KS, 4, 8, 4, 2, 1, 1>(X, ldx, Cm2, N, Kp, d, labels, sums, ld, op, md, s); \
-    default: return HARP_EBADARG;                                                           \
+#define KM_VARIANT_TABLE(ROW, KS) \
+  ROW(KS, 4, 1, 16, 2, 0, 0, 0)   \
+  ROW(KS, 13, 4, 8, 2, 2, 0, 0)   \
+  ROW(KS, 14, 4, 8, 4, 2, 0, 0)   \
+  ROW(KS, 15, 4, 8, 4, 2, 1, 0)   \
+  ROW(KS, 16, 4, 8, 4, 2, 1, 1)
+#define KM_LAUNCH_ROW(KS, V, G, WAVES, RG, PIPE, PRIO, KEYLESS) \
+  case V: return launch_assign<KS, G, WAVES, RG, PIPE, PRIO, KEYLESS>(X, ldx, Cm2, N, Kp, d, labels, sums, ld, op, md, s);
+#define KM_PTS_ROW(KS, V, G, WAVES, RG, PIPE, PRIO, KEYLESS) \
+  case V: return KMCfg<KS, G, WAVES, RG>::PTS;
+#define KM_VARIANTS(KS)                      \
+  switch (variant) {                         \
+    KM_VARIANT_TABLE(KM_LAUNCH_ROW, KS)      \
+    default: return HARP_EBADARG;            \
   }
 
 }  // namespace
 
 HARP_EXPORT int harp_kmeans_points_per_block(int variant) {
   switch (variant) {
-    case 4: return 16 * 1 * 32;
-    case 13: case 14: case 15: case 16: return 8 * 4 * 32;
+    KM_VARIANT_TABLE(KM_PTS_ROW, 1)  // PTS does not depend on the k-steps
     default: return -1;
   }
 }
@@ -972,10 +834,11 @@ HARP_EXPORT int harp_kmeans_assign(const void* X, long ldx, const void* Cm2, lon
 
 // Wide rows (dp > 256, dp % 64 == 0): keys (N uint64, filled with ~0 by the caller) take the
 // per-point (distance, index) minimum over all centroid blocks; harp_kmeans_wide_finish then
-// writes labels / distances / objective partials (one per 256 points). variant: 0 = 6 (both
-// operands through LDS-DMA into a 256 x 256 tile, 8 waves = 2 per SIMD, each 128 centroids x
-// 64 points); 5 = the same tile with 4 waves (256 centroids x 64 points each); 1 / 3 =
-// point fragments loaded straight into registers (2 groups at 1 wave / SIMD, 1 group at 2).
+// writes labels / distances / objective partials (one per 256 points). variant: 0 = 6 (the
+// ring kernel: both operands through LDS-DMA into a 256 x 256 tile, 8 waves = 2 per SIMD,
+// each 128 centroids x 64 points); 5 = the same kernel with 4 waves (256 centroids x 64
+// points each); 1 / 3 = the register kernel, point fragments loaded straight into registers
+// (2 groups at 1 wave / SIMD, 1 group at 2).
 // Measured at N = 1e7, K = 1e3 (profiles/r4_kwide): d = 1000 6 and 5 both 0.98 PF useful,
 // d = 512 6 at 0.86 vs 5 at 0.81 PF; 1 / 3 at 0.56 / 0.61 (waves parked 52-66 % of their
 // cycles on 32-row-per-instruction point loads); 128-feature stages, a 3-deep register
@@ -989,10 +852,10 @@ HARP_EXPORT int harp_kmeans_assign_wide(const void* X, long ldx, const void* Cm2
     return HARP_EBADARG;
   if (variant == 0) variant = 6;
   switch (variant) {
-    case 1: return launch_wide<2, 64, 1>(X, ldx, Cm2, N, dp, kswept, kp, keys, s);
-    case 3: return launch_wide<1, 64, 2>(X, ldx, Cm2, N, dp, kswept, kp, keys, s);
-    case 5: return launch_wide_lds<2, 64, 2>(X, ldx, Cm2, N, dp, kswept, kp, keys, s);
-    case 6: return launch_wide8<2, 64, 2>(X, ldx, Cm2, N, dp, kswept, kp, keys, s);
+    case 1: return launch_wide(wide_reg<2, 64, 1>, X, ldx, Cm2, N, dp, kswept, kp, keys, s);
+    case 3: return launch_wide(wide_reg<1, 64, 2>, X, ldx, Cm2, N, dp, kswept, kp, keys, s);
+    case 5: return launch_wide(wide_ring<2, 64, 2, 4>, X, ldx, Cm2, N, dp, kswept, kp, keys, s);
+    case 6: return launch_wide(wide_ring<2, 64, 2, 8>, X, ldx, Cm2, N, dp, kswept, kp, keys, s);
     default: return HARP_EBADARG;
   }
 }

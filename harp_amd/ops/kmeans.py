@@ -24,7 +24,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _lib, segment
 
 KP_ALIGN = 128
 ONES = 4  # X columns d..d+3 hold 1.0
@@ -149,13 +149,23 @@ def swept_k(op: "CentroidOperand") -> int:
     return min(op.Cm2.shape[0], (op.K + 31) // 32 * 32)
 
 
+def _check_operands(X, op):
+    assert X.dtype == torch.bfloat16 and X.stride(1) == 1 and X.stride(0) % 8 == 0 and op.Cm2.shape[1] == X.shape[1]
+
+
+def _check_sums(sums, op, dev):
+    assert sums.dtype == torch.float32 and sums.shape[1] >= op.d + 1 and sums.is_contiguous()
+    assert sums.shape[0] >= op.Cm2.shape[0], "sums needs Kp (padded) rows"
+    assert sums.device == dev
+
+
 def _assign_wide(X, op, sums, labels, want_objective, obj_partial, min_dist):
-    """dp > 256 (any d): the feature-staged kernel (csrc/kmeans.hip kmeans_assign_wide_kernel)
-    merges per-centroid-block minima with 64-bit atomics, then the bucketed gather-sum."""
+    """dp > 256 (any d): the feature-staged kernels (csrc/kmeans.hip, the ring kernel by
+    default) merge per-centroid-block minima with 64-bit atomics, then the bucketed gather-sum."""
     n, dp = X.shape
     dev = X.device
     lib = _lib.kernels()
-    assert X.dtype == torch.bfloat16 and X.stride(1) == 1 and X.stride(0) % 8 == 0 and op.Cm2.shape[1] == dp
+    _check_operands(X, op)
     assert dp % WIDE_ALIGN == 0, f"wide rows need dp % {WIDE_ALIGN} == 0 (pack with padded_dim)"
     keys = torch.full((n,), -1, dtype=torch.int64, device=dev)  # all ones: +inf distance
     _lib.check(lib.harp_kmeans_assign_wide(X.data_ptr(), X.stride(0), op.Cm2.data_ptr(), n, dp, swept_k(op),
@@ -169,11 +179,7 @@ def _assign_wide(X, op, sums, labels, want_objective, obj_partial, min_dist):
                                            min_dist.data_ptr() if min_dist is not None else None,
                                            _lib.stream_ptr(dev)), "kmeans_wide_finish")
     if sums is not None:
-        from . import segment
-
-        assert sums.dtype == torch.float32 and sums.shape[1] >= op.d + 1 and sums.is_contiguous()
-        assert sums.shape[0] >= op.Cm2.shape[0], "sums needs Kp (padded) rows"
-        assert sums.device == dev
+        _check_sums(sums, op, dev)
         perm, start = segment.bucket_labels(labels, op.Cm2.shape[0])
         segment.bucket_rowsum(X, perm, start, sums)
     obj = obj_partial[:nblk].double().sum() if want_objective else None
@@ -225,10 +231,8 @@ def assign(X: torch.Tensor, op: CentroidOperand, sums: Optional[torch.Tensor] = 
         if want_objective and (obj_partial is None or obj_partial.numel() < nblk):
             obj_partial = torch.empty(nblk, dtype=torch.float32, device=dev)
         if sums is not None:
-            assert sums.dtype == torch.float32 and sums.shape[1] >= op.d + 1 and sums.is_contiguous()
-            assert sums.shape[0] >= op.Cm2.shape[0], "sums needs Kp (padded) rows"
-            assert sums.device == dev
-        assert X.dtype == torch.bfloat16 and X.stride(1) == 1 and X.stride(0) % 8 == 0 and op.Cm2.shape[1] == dp
+            _check_sums(sums, op, dev)
+        _check_operands(X, op)
         fused = sums if accumulate == "atomic" else None
         bucket = sums is not None and fused is None
         chunks = pipeline_chunks(n, ppb) if bucket else 1
@@ -248,7 +252,6 @@ def assign(X: torch.Tensor, op: CentroidOperand, sums: Optional[torch.Tensor] = 
             _lib.check(st, "kmeans_assign")
             if not bucket:
                 continue
-            from . import segment
 
             def bucket_sum(lab, Xc):
                 if keyless:  # lab holds 32-row group ids: sort by group, resolve the row, sum
