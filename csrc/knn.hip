@@ -90,8 +90,12 @@ __global__ __launch_bounds__(256) void knn_select_kernel(const float* __restrict
   }
   const float qq = qn[q];
   const float* row = S + q * lds;
-  int j = lane;
-  for (int it = 0; j + 192 < N; j += 256, ++it) {
+  // The 4-way trips are taken by the whole wave or not at all (the bound is lane 63's): the
+  // threshold update inside is a wave reduction, and a lane that has left the loop would
+  // feed it a zero. The last, partial group of 256 columns goes to the 64-stride tail.
+  int base = 0;
+  for (int it = 0; base + 255 < N; base += 256, ++it) {
+    const int j = base + lane;
     if ((it & 3) == 3) thr = fminf(thr, wave_min_f32(dl[KK - 1]));
     const float s0 = row[j], s1 = row[j + 64], s2 = row[j + 128], s3 = row[j + 192];
     const float t0 = tn[j], t1 = tn[j + 64], t2 = tn[j + 128], t3 = tn[j + 192];
@@ -102,7 +106,7 @@ __global__ __launch_bounds__(256) void knn_select_kernel(const float* __restrict
     if (d2 < fminf(dl[KK - 1], thr)) list_insert<KK>(dl, il, d2, col0 + j + 128);
     if (d3 < fminf(dl[KK - 1], thr)) list_insert<KK>(dl, il, d3, col0 + j + 192);
   }
-  for (; j < N; j += 64) {
+  for (int j = base + lane; j < N; j += 64) {
     const float d = fmaxf(fmaf(-2.f, row[j], qq + tn[j]), 0.f);
     if (d < fminf(dl[KK - 1], thr)) list_insert<KK>(dl, il, d, col0 + j);
   }

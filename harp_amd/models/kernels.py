@@ -195,6 +195,8 @@ def em_gmm(X: torch.Tensor, K: int, comm: Optional[Communicator] = None, n_itera
     from ..ops import gmm as GM
 
     native = GM.usable(Xd) and estep != "torch"
+    if native:
+        Xd = GM.row_major(Xd)  # a strided view is copied once, not in every iteration
     for it in range(n_iterations):
         if native:
             R, llsum = GM.estep(Xd, w, mu, cov, covariance)

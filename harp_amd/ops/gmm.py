@@ -42,6 +42,18 @@ def usable(X: torch.Tensor) -> bool:
         and _lib.use_native(X)
 
 
+def row_major(X: torch.Tensor) -> torch.Tensor:
+    """X as the kernels read it: unit inner stride and a row stride >= d. A view with
+    another layout (``Xw[:, ::2]``, ``Y.t()``) is copied; ``Xw[:, a:b]`` is passed as it is."""
+    if X.stride(1) != 1 or (X.shape[0] > 1 and X.stride(0) < X.shape[1]):
+        return X.contiguous()
+    return X
+
+
+def _ldx(X: torch.Tensor) -> int:
+    return X.stride(0) if X.shape[0] > 1 else X.shape[1]  # one row: its stride is never used
+
+
 _AUG: Dict[tuple, Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = {}
 
 
@@ -90,13 +102,14 @@ def whiten(w: torch.Tensor, mu: torch.Tensor, cov: torch.Tensor, covariance: str
 def estep(X: torch.Tensor, w: torch.Tensor, mu: torch.Tensor, cov: torch.Tensor, covariance: str = "full"):
     """Responsibilities R [n, K] (a transposed view of component-major storage) and the
     summed log-likelihood sum_n log sum_k w_k N(x_n | k)."""
+    X = row_major(X)
     n, d = X.shape
     K = mu.shape[0]
     Paug, b = whiten(w, mu, cov, covariance)
     RT = torch.empty((K, n), dtype=torch.float64, device=X.device)  # component-major (coalesced writes)
     lib = _lib.kernels()
     part = torch.zeros(max(int(lib.harp_gmm_estep_blocks(n, d)), 1), dtype=torch.float64, device=X.device)
-    st = lib.harp_gmm_estep(X.data_ptr(), X.stride(0), n, d, K, Paug.data_ptr(), b.data_ptr(),
+    st = lib.harp_gmm_estep(X.data_ptr(), _ldx(X), n, d, K, Paug.data_ptr(), b.data_ptr(),
                             RT.data_ptr(), RT.stride(0), part.data_ptr(), _lib.stream_ptr(X.device))
     _lib.check(st, "gmm_estep")
     return RT.t(), part.sum()
@@ -117,6 +130,7 @@ def _pairs(d: int, covariance: str, device) -> Tuple[torch.Tensor, torch.Tensor]
 
 def stats(X: torch.Tensor, R: torch.Tensor, covariance: str = "full"):
     """(N_k [K], S1 = sum r x [K, d], S2 = sum r x x^T [K, d, d] (full) or sum r x^2 [K, d]) in one pass."""
+    X = row_major(X)
     n, d = X.shape
     K = R.shape[1]
     RT = R.t() if (R.stride(0) == 1 and R.t().is_contiguous()) else R.t().contiguous()  # component-major
@@ -126,20 +140,23 @@ def stats(X: torch.Tensor, R: torch.Tensor, covariance: str = "full"):
         nbk = int(lib.harp_gmm_coord_blocks(d))
         npb = nbk * (nbk + 1) // 2
         Sb = torch.zeros((K, npb, 16), dtype=torch.float64, device=X.device)
-        st = lib.harp_gmm_stats_blocks(X.data_ptr(), X.stride(0), n, d, RT.data_ptr(), RT.stride(0), K,
+        st = lib.harp_gmm_stats_blocks(X.data_ptr(), _ldx(X), n, d, RT.data_ptr(), RT.stride(0), K,
                                        Sb.data_ptr(), _lib.stream_ptr(X.device))
         _lib.check(st, "gmm_stats_blocks")
         bi, bj = torch.triu_indices(nbk, nbk, device=X.device)
         M = torch.zeros((K, nbk, nbk, 4, 4), dtype=torch.float64, device=X.device)
         blocks = Sb.view(K, npb, 4, 4)
-        M[:, bj, bi] = blocks.transpose(2, 3)  # the lower block triangle mirrors the upper
         M[:, bi, bj] = blocks
         M = M.permute(0, 1, 3, 2, 4).reshape(K, 4 * nbk, 4 * nbk)[:, :d + 1, :d + 1]
+        # the lower triangle mirrors the upper entry by entry: a diagonal block is computed
+        # whole, and with several point blocks its (u, v) and (v, u) sums meet their atomics
+        # in different orders, so they agree only to rounding
+        M = torch.triu(M) + torch.triu(M, 1).transpose(1, 2)
         return M[:, d, d].contiguous(), M[:, :d, d].contiguous(), M[:, :d, :d].contiguous()
     pi, pj = _pairs(d, covariance, X.device)
     npairs = pi.numel()
     S = torch.zeros((K, npairs), dtype=torch.float64, device=X.device)
-    st = _lib.kernels().harp_gmm_stats(X.data_ptr(), X.stride(0), n, d, RT.data_ptr(), RT.stride(0), K,
+    st = _lib.kernels().harp_gmm_stats(X.data_ptr(), _ldx(X), n, d, RT.data_ptr(), RT.stride(0), K,
                                        pi.data_ptr(), pj.data_ptr(), npairs, S.data_ptr(), _lib.stream_ptr(X.device))
     _lib.check(st, "gmm_stats")
     if covariance == "full":

@@ -54,3 +54,32 @@ def test_color_count_gpu_equals_cpu_and_brute_force(cuda, k):
     cpu = color_count(Communicator(None, torch.device("cpu")), T, src, dst, n, colors)
     assert gpu == cpu
     assert round(gpu) == brute_force_embeddings(T, e, n, colors.tolist())
+
+
+def _skewed(n, m, n_src, C, seed):
+    g = torch.Generator().manual_seed(seed)
+    rows = (torch.rand(m, generator=g) ** 2 * n).long()  # skewed degrees, some empty rows
+    cols = torch.randint(0, n_src, (m,), generator=g)
+    M = torch.rand(n_src, C, generator=g, dtype=torch.float64)
+    return rows, cols, M
+
+
+@pytest.mark.parametrize("C", [2, 4, 5, 8, 16, 17, 32, 33])
+def test_csr_spmm_every_width(cuda, C):
+    """C = 2, 8 and 32 launch csr_spmm_kernel<2>, <8> and <32>; 5, 17 and 33 leave padding
+    lanes in <8>, <32> and <64>."""
+    n = 5000
+    rows, cols, M = _skewed(n, 80000, 3000, C, 1000 + C)
+    ref = torch.zeros(n, C, dtype=torch.float64).index_add_(0, rows, M[cols])
+    out = G.spmm(G.build_csr(rows.to(cuda), cols.to(cuda), n), M.to(cuda))
+    assert torch.allclose(out.cpu(), ref, rtol=1e-12, atol=1e-12)
+
+
+def test_csr_spmm_grid_stride(cuda):
+    """300000 vertices at four per block are more than 65536 blocks: the grid-stride loop runs."""
+    n, C = 300000, 3
+    assert (n + 3) // 4 > 65536
+    rows, cols, M = _skewed(n, 600000, 3000, C, 2)
+    ref = torch.zeros(n, C, dtype=torch.float64).index_add_(0, rows, M[cols])
+    out = G.spmm(G.build_csr(rows.to(cuda), cols.to(cuda), n), M.to(cuda))
+    assert torch.allclose(out.cpu(), ref, rtol=1e-12, atol=1e-12)

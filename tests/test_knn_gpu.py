@@ -60,3 +60,73 @@ def test_knn_rejects_unsupported(cuda):
         KN.knn_search(t, t, 33)
     with pytest.raises(TypeError):
         KN.knn_search(t.double(), t.double(), 3)
+
+
+# ---------------------------------------------------------------------------------------
+# Exact data: integer coordinates in [0, 16) stored as fp32, d <= 64. Every product, norm
+# and GEMM sum is an integer below 2^24, exact in fp32 in any order, so the kernel's
+# distances equal the fp64 distances bit for bit and its indices equal a stable ascending
+# sort of the fp64 distance rows entry for entry: no tolerance, no agreement fraction. The
+# data is full of duplicates and equal distances, so the tie rule (lower train index) is
+# checked on every row.
+def _int_points(n, d, g):
+    return torch.randint(0, 16, (n, d), generator=g).float()
+
+
+def _assert_exact(cuda, train, queries, k, q_tile, t_tile):
+    D = (queries.double()[:, None, :] - train.double()[None, :, :]).pow(2).sum(-1)
+    rd, ri = torch.sort(D, dim=1, stable=True)
+    kk = min(k, train.shape[0])
+    od, oi = KN.knn_search(train.to(cuda), queries.to(cuda), k, q_tile=q_tile, t_tile=t_tile)
+    assert od.shape == oi.shape == (queries.shape[0], kk) and oi.dtype == torch.int64
+    assert torch.equal(od.double().cpu(), rd[:, :kk])
+    assert torch.equal(oi.cpu(), ri[:, :kk])
+
+
+# (train rows, t_tile): train-tile widths 64 + 1, 64 + 63, 320 + 65, 256 + 255, 257 + 257,
+# 256 + 256 + 1 (the 4-way loop with and without a tail, the tail alone), and 1000 and
+# 1023, where the fourth trip of the 4-way loop is entered by some lanes of a wave only
+@pytest.mark.parametrize("n,t_tile", [(65, 64), (127, 64), (385, 320), (511, 256), (514, 257), (513, 256),
+                                      (1000, 1024), (2023, 1023)])
+@pytest.mark.parametrize("k", [4, 8, 9, 17, 32])
+def test_knn_exact_list_lengths_and_tile_widths(cuda, k, n, t_tile):
+    g = torch.Generator().manual_seed(31 * n + k)
+    train, queries = _int_points(n, 5, g), _int_points(5, 5, g)
+    _assert_exact(cuda, train, queries, k, 4, t_tile)  # the second query tile: one row at an offset
+
+
+def test_knn_exact_merge_into_empty_slots(cuda):
+    """The first train tiles are shorter than k, so the running state carries index -1 slots
+    into the next merges; and fewer train rows than k return that many columns."""
+    g = torch.Generator().manual_seed(77)
+    _assert_exact(cuda, _int_points(40, 64, g), _int_points(5, 64, g), 16, 4, 5)
+    _assert_exact(cuda, _int_points(3, 7, g), _int_points(5, 7, g), 5, 4, 1 << 16)
+    _assert_exact(cuda, _int_points(3, 7, g), _int_points(5, 7, g), 5, 4, 2)
+
+
+@pytest.mark.parametrize("k", [10, 32])
+def test_knn_exact_ties_across_train_tiles(cuda, k):
+    g = torch.Generator().manual_seed(5)
+    points = _int_points(6, 8, g)
+    train = points[torch.randint(0, 6, (700,), generator=g)]
+    queries = torch.cat([points[:3], _int_points(2, 8, g)])
+    _assert_exact(cuda, train, queries, k, 4, 256)
+
+
+def test_knn_cancellation_is_clamped(cuda):
+    """Queries are copies of train rows with coordinates near 1e3: |q|^2 + |t|^2 - 2 q.t
+    cancels seven digits. Own-distances come out clamped at >= 0, nothing is NaN, and every
+    returned distance is within 2 d 2^-24 (|q|^2 + |t|^2) of the fp64 distance to the row it
+    names (the worst-case rounding of a d-term fp32 dot product plus the three additions)."""
+    g = torch.Generator().manual_seed(8)
+    d, n, M, k = 16, 300, 64, 8
+    train = 1e3 + torch.randn(n, d, generator=g)
+    queries = train[torch.randperm(n, generator=g)[:M]].clone()
+    od, oi = KN.knn_search(train.to(cuda), queries.to(cuda), k, q_tile=48, t_tile=128)
+    od, oi = od.double().cpu(), oi.cpu()
+    assert not torch.isnan(od).any() and (od >= 0).all() and (od[:, 1:] >= od[:, :-1]).all()
+    assert ((oi >= 0) & (oi < n)).all()
+    exact = (train[oi].double() - queries.double()[:, None, :]).pow(2).sum(-1)
+    qq, tt = queries.double().pow(2).sum(1), train.double().pow(2).sum(1)
+    bound = 2 * d * 2.0 ** -24 * (qq[:, None] + tt[oi])
+    assert ((od - exact).abs() <= bound).all(), ((od - exact).abs() / bound).max()

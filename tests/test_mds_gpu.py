@@ -10,7 +10,24 @@ from harp_amd.parallel.comm import Communicator
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("dim", [2, 3, 4])
+def _direct_rows(D, W, row0, X, diff):
+    """B(Z) X and the stress of the rows with distances from coordinate differences, as the
+    kernel forms them. The model's CPU path takes them from the Gram matrix, which loses
+    |x|^2 * 2^-52 / d_ij^2: nothing at dim >= 2 here (closest pair 1e-3), but 1e-6 of a
+    B(Z) X entry at dim = 1, where 700 points on a line have pairs 2e-6 apart."""
+    n_r = D.shape[0]
+    Xr = X[row0:row0 + n_r]
+    Dz = (Xr[:, None, :] - X[None, :, :]).pow(2).sum(-1).sqrt()
+    off = torch.ones_like(Dz, dtype=torch.bool)
+    off[torch.arange(n_r), torch.arange(n_r) + row0] = False
+    ok = off & (W != 0) & (Dz >= 1e-10) & (D > diff)
+    B = torch.where(ok, -W * (D - diff) / Dz.clamp_min(1e-10), torch.zeros_like(Dz))
+    bc = B @ X - B.sum(1, keepdim=True) * Xr
+    dd = D - diff - Dz
+    return bc, (W * dd * dd * ((W != 0) & (D >= diff))).sum()
+
+
+@pytest.mark.parametrize("dim", [1, 2, 3, 4])
 @pytest.mark.parametrize("T", [0.0, 0.05])
 def test_bc_and_stress_match_torch(cuda, dim, T):
     g = torch.Generator().manual_seed(dim)
@@ -24,10 +41,15 @@ def test_bc_and_stress_match_torch(cuda, dim, T):
     cpu = MD._Rows(comm, D, W, row0)
     gpu = MD._Rows(Communicator(None, cuda), D.to(cuda), W.to(cuda), row0)
     assert gpu._native(X.to(cuda))
-    bc_ref, bc = cpu.bc(X, T, dim), gpu.bc(X.to(cuda), T, dim).cpu()
-    assert torch.allclose(bc, bc_ref, rtol=1e-9, atol=1e-9 * bc_ref.abs().max().item())
-    s_ref, s = cpu.stress(X, T, dim), gpu.stress(X.to(cuda), T, dim).cpu()
+    bc, s = gpu.bc(X.to(cuda), T, dim).cpu(), gpu.stress(X.to(cuda), T, dim).cpu()
+    bc_dir, s_dir = _direct_rows(D, W, row0, X, math.sqrt(2.0 * dim) * T if T > 1e-9 else 0.0)
+    assert torch.allclose(bc, bc_dir, rtol=1e-9, atol=1e-9 * bc_dir.abs().max().item())
+    assert math.isclose(float(s), float(s_dir), rel_tol=1e-9)
+    s_ref = cpu.stress(X, T, dim)
     assert math.isclose(float(s), float(s_ref), rel_tol=1e-9)
+    if dim >= 2:  # see _direct_rows: at dim = 1 the CPU path itself is 1e-6 off
+        bc_ref = cpu.bc(X, T, dim)
+        assert torch.allclose(bc, bc_ref, rtol=1e-9, atol=1e-9 * bc_ref.abs().max().item())
 
 
 def test_wdamds_gpu_equals_cpu(cuda):

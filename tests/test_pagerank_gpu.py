@@ -65,3 +65,22 @@ def test_pagerank_app_on_gpu(cuda):
     want = _ref_pagerank(src, dst, n, 20)
     assert torch.allclose(pr.cpu(), want, rtol=1e-12, atol=1e-15)
     assert abs(float(pr.sum()) - 1.0) < 1e-9
+
+
+def test_pull_step_grid_stride(cuda):
+    """n = 300000 at average in-degree 33 selects G = 64 lanes per row: 75000 blocks, more
+    than the 65536 launched, so the grid-stride loop takes a second, partial sweep."""
+    n, avg = 300000, 33
+    assert avg > 32 and (n * 64 + 255) // 256 > 65536
+    src, dst = _graph(n, avg, 33)
+    g = torch.Generator().manual_seed(34)
+    x = torch.rand(n, generator=g, dtype=torch.float64)
+    invdeg = torch.rand(n, generator=g, dtype=torch.float64)
+    dm = torch.tensor([0.125], dtype=torch.float64)
+    want = torch.zeros(n, dtype=torch.float64)
+    want.index_add_(0, dst, x[src])
+    want = 0.85 * want + 0.01 + 0.5 * dm
+    csr = GO.build_csr(dst.to(cuda), src.to(cuda), n)
+    out, xn = GO.pagerank_pull(csr, x.to(cuda), 0.85, 0.01, 0.5, dm.to(cuda), invdeg.to(cuda), want_xnext=True)
+    assert torch.allclose(out.cpu(), want, rtol=1e-13, atol=1e-13)
+    assert torch.allclose(xn.cpu(), want * invdeg, rtol=1e-13, atol=1e-13)
