@@ -114,19 +114,24 @@ __global__ __launch_bounds__(WAVES * 64) void kmeans_assign_kernel(
   // searched only on improvement measured 5 % slower (it spills; profiles/r2_ktail).
   // KEYLESS (variant 16): the plain minimum of the 16 candidates, no index bits. The sweep then
   // knows only the winning 32-row group; the row inside it is found by the gather-sum pass,
-  // which re-computes that one group's 32 distances per point (kmeans_resolve.hip).
+  // which re-computes that one group's 32 distances per point (kmeans_resolve.hip). Its min
+  // chain starts from best[g] itself: eight v_min3, one compare and one select per tile (10
+  // VALU, 1.56 per MFMA at 7 k-steps) where the minimum of the 16 first and a compare against
+  // best[g] after took 13 (profiles/r9_sweep_pipe). The keyed form stays: folded the same way
+  // its RG=2 tiling (variant 13) spills at 7 k-steps.
   auto tile_argmin = [&](const floatx16& ac, int g, int tg) {
-    float m;
     if constexpr (KEYLESS) {
-      m = ac[0];
+      float nb = best[g];
 #pragma unroll
-      for (int q = 1; q < 16; ++q) m = fminf(m, ac[q]);
+      for (int q = 0; q < 16; q += 2) nb = fminf(fminf(nb, ac[q]), ac[q + 1]);
+      if (nb < best[g]) bestt[g] = tg;
+      best[g] = nb;
     } else {
-      m = keyed(ac[0], 0u);
+      float m = keyed(ac[0], 0u);
 #pragma unroll
       for (int q = 1; q < 16; ++q) m = fminf(m, keyed(ac[q], (unsigned)q));
+      if (m < best[g]) { best[g] = m; bestt[g] = tg; }
     }
-    if (m < best[g]) { best[g] = m; bestt[g] = tg; }
   };
 
   // per-lane byte offsets of its A-fragment chunks inside a 32-row group
@@ -151,8 +156,12 @@ __global__ __launch_bounds__(WAVES * 64) void kmeans_assign_kernel(
     for (int s = 0; s < KS; ++s) af[0][s] = *(const bf16x8*)(buf + aoff[s]);
     if constexpr (PIPE > 0) {
       // software pipeline over the stage's RG*G (row group, point group) items: the MFMA
-      // chain of item i+1 is issued before the argmin epilogue of item i, so the epilogue's
-      // VALU work fills the MFMA gaps instead of waiting on the chain's tail latency
+      // chain of item i+1 stands in front of the argmin epilogue of item i, so most of the
+      // epilogue's VALU work sits in the next chain's MFMA gaps. hipcc still puts the head of
+      // epilogue i and its hazard wait (s_nop 11) between the two chains; forcing five MFMAs of
+      // chain i+1 in front of it with a scheduling fence removes the wait from the stream and
+      // measured 0.6 ms of 132 (two waves share the SIMD's matrix pipe and fill each other's
+      // holes), too little to keep (profiles/r9_sweep_pipe)
       constexpr int NI = RG * G;
       floatx16 acc[2];
 #pragma unroll

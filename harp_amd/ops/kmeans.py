@@ -30,10 +30,10 @@ KP_ALIGN = 128
 ONES = 4  # X columns d..d+3 hold 1.0
 # (G4, W8, RG4, pipelined; 1024 points per workgroup) with static VALU priority for waves 4-7
 # (15; 14 without it: 0.2 % slower, profiles/r3_setprio). 16 is the keyless form of 15: the
-# sweep finds only the winning 32-row centroid group (no index bits in the distances: 2.0
+# sweep finds only the winning 32-row centroid group (no index bits in the distances: 1.6
 # instead of 4.3 VALU instructions per MFMA) and the bucketed gather-sum pass, which reads
 # every row anyway, finds the row inside the group (csrc/kmeans_resolve.hip;
-# profiles/r7_keyless). Calls without a bucketed sum to resolve in run 15.
+# profiles/r7_keyless, r9_sweep_pipe). Calls without a bucketed sum to resolve in run 15.
 DEFAULT_VARIANT = 16
 KEYLESS_VARIANT, KEYED_VARIANT = 16, 15
 KEYLESS_MAX_DP = 128
