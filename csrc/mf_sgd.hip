@@ -30,6 +30,7 @@
 #include "common.h"
 
 #include <climits>
+#include <type_traits>
 
 namespace {
 
@@ -471,6 +472,19 @@ __device__ __forceinline__ void placement_check(unsigned long long* chk, unsigne
     __hip_atomic_store(chk + kChkErr, 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The cell XCD row x trains in sub-step `step`: its ratings are [a, a + ncell) of
+// rows/cols/vals, of which the n from position w0 on (wrapping around the cell) are trained
+struct Cell {
+  long a, ncell, w0, n;
+};
+
+__device__ __forceinline__ Cell cell_of(const long* off, const long* win, int x, int step) {
+  const int cell = x * XCDS + (x + step) % XCDS;
+  const long a = off[cell];
+  const long ncell = off[cell + 1] - a;
+  return {a, ncell, win ? win[cell] : 0, win ? win[XCDS * XCDS + cell] : ncell};
+}
+
 template <int R, int CH, int ATOM>
 __global__ __launch_bounds__(256) void mf_sgd_xcd_kernel(const int* __restrict__ rows, const int* __restrict__ cols,
                                                          const float* __restrict__ vals, const long* __restrict__ off,
@@ -483,31 +497,29 @@ __global__ __launch_bounds__(256) void mf_sgd_xcd_kernel(const int* __restrict__
   const int x = blockIdx.x % XCDS;
   const long j = blockIdx.x / XCDS;
   const long per_xcd = gridDim.x / XCDS;
-  const int cell = x * XCDS + (x + step) % XCDS;
-  const long a = off[cell];
-  const long ncell = off[cell + 1] - a;
-  const long w0 = win ? win[cell] : 0;
-  const long n = win ? win[XCDS * XCDS + cell] : ncell;
-  const long nst = (n + CH - 1) / CH;
+  const Cell c = cell_of(off, win, x, step);
+  const long nst = (c.n + CH - 1) / CH;
   const int sl = threadIdx.x & 15;
   const int sub = threadIdx.x >> 4;  // 16 streams per 256-thread block
+  // the round of xcd_round below, kept inline: routed through the helper, this kernel's
+  // VGPR counts rise in a third of its instantiations (profiles/sgd_shared_pieces)
   for (long st0 = j * 16; st0 < nst; st0 += per_xcd * 16) {
     const long r0 = st0 * CH;
     __syncthreads();  // the previous round is done with the LDS triples
     for (int k = threadIdx.x; k < 16 * CH; k += 256) {
-      if (r0 + k < n) {
-        long q = w0 + r0 + k;
-        if (q >= ncell) q -= ncell;
-        sR[k] = rows[a + q];
-        sC[k] = cols[a + q];
-        sV[k] = vals[a + q];
+      if (r0 + k < c.n) {
+        long q = c.w0 + r0 + k;
+        if (q >= c.ncell) q -= c.ncell;
+        sR[k] = rows[c.a + q];
+        sC[k] = cols[c.a + q];
+        sV[k] = vals[c.a + q];
       }
     }
     __syncthreads();
-    const long mine = n - (r0 + (long)sub * CH);
+    const long mine = c.n - (r0 + (long)sub * CH);
     if (mine > 0)
       sgd_stream_lds<R, false, ATOM>(sR + sub * CH, sC + sub * CH, sV + sub * CH, mine < CH ? (int)mine : CH, sl, W,
-                             (unsigned)ldw, H, (unsigned)ldh, lr, lam);
+                                     (unsigned)ldw, H, (unsigned)ldh, lr, lam);
   }
   placement_check(chk, gen, x);
 }
@@ -523,7 +535,12 @@ __global__ __launch_bounds__(256) void mf_sgd_xcd_kernel(const int* __restrict__
 // ws layout (int32): claim[8] | exit | drained
 constexpr int kPlacedWs = 10;
 
-template <int R, int CH, int ATOM>
+// Round `rd` of a cell, run by a 256-thread block: the 16*CH index triples from window
+// position rd*16*CH on go to LDS in one contiguous, coalesced copy (wrapping around the
+// cell), then each 16-lane subgroup runs one stream of CH of them (the window's last stream
+// may be shorter, the subgroups past it idle). SYNC_FIRST: wait until the block's previous
+// round is done with the LDS triples; the flow kernel syncs after its rounds instead.
+template <int R, int CH, int ATOM, bool WL2 = false, bool SYNC_FIRST = true>
 __device__ __forceinline__ void xcd_round(const int* __restrict__ rows, const int* __restrict__ cols,
                                           const float* __restrict__ vals, long a, long w0, long ncell, long n, long rd,
                                           int* sR, int* sC, float* sV, float* __restrict__ W, int ldw,
@@ -531,7 +548,7 @@ __device__ __forceinline__ void xcd_round(const int* __restrict__ rows, const in
   const int sl = threadIdx.x & 15;
   const int sub = threadIdx.x >> 4;
   const long r0 = rd * 16 * CH;
-  __syncthreads();  // the previous round is done with the LDS triples
+  if constexpr (SYNC_FIRST) __syncthreads();
   for (int k = threadIdx.x; k < 16 * CH; k += 256) {
     if (r0 + k < n) {
       long q = w0 + r0 + k;
@@ -544,9 +561,8 @@ __device__ __forceinline__ void xcd_round(const int* __restrict__ rows, const in
   __syncthreads();
   const long left = n - (r0 + (long)sub * CH);
   if (left > 0)
-    sgd_stream_lds<R, false, ATOM>(sR + sub * CH, sC + sub * CH, sV + sub * CH, left < CH ? (int)left : CH, sl, W,
-                                   (unsigned)ldw, H,
-                      (unsigned)ldh, lr, lam);
+    sgd_stream_lds<R, WL2, ATOM>(sR + sub * CH, sC + sub * CH, sV + sub * CH, left < CH ? (int)left : CH, sl, W,
+                                 (unsigned)ldw, H, (unsigned)ldh, lr, lam);
 }
 
 template <int R, int CH, int ATOM>
@@ -561,16 +577,8 @@ __global__ __launch_bounds__(256) void mf_sgd_xcd_placed_kernel(const int* __res
   __shared__ float sV[16 * CH];
   __shared__ int s_round, s_last;
   const int x = hw_xcc_id() & (XCDS - 1);
-  auto cell_of = [&](int xx, long& a, long& w0, long& ncell, long& n) {
-    const int cell = xx * XCDS + (xx + step) % XCDS;
-    a = off[cell];
-    ncell = off[cell + 1] - a;
-    w0 = win ? win[cell] : 0;
-    n = win ? win[XCDS * XCDS + cell] : ncell;
-  };
-  long a, w0, ncell, n;
-  cell_of(x, a, w0, ncell, n);
-  const long rounds = (n + 16 * CH - 1) / (16 * CH);
+  Cell c = cell_of(off, win, x, step);
+  const long rounds = (c.n + 16 * CH - 1) / (16 * CH);
   for (;;) {
     if (threadIdx.x == 0)
       s_round = __hip_atomic_fetch_add(ws + x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -578,7 +586,7 @@ __global__ __launch_bounds__(256) void mf_sgd_xcd_placed_kernel(const int* __res
     const long rd = s_round;
     __syncthreads();  // everyone read s_round before it is rewritten
     if (rd >= rounds) break;
-    xcd_round<R, CH, ATOM>(rows, cols, vals, a, w0, ncell, n, rd, sR, sC, sV, W, ldw, H, ldh, lr, lam);
+    xcd_round<R, CH, ATOM>(rows, cols, vals, c.a, c.w0, c.ncell, c.n, rd, sR, sC, sV, W, ldw, H, ldh, lr, lam);
   }
   if (threadIdx.x == 0)
     s_last = __hip_atomic_fetch_add(ws + 8, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
@@ -586,10 +594,10 @@ __global__ __launch_bounds__(256) void mf_sgd_xcd_placed_kernel(const int* __res
   if (!s_last) return;
   for (int xx = 0; xx < XCDS; ++xx) {
     if (__hip_atomic_load(ws + xx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) continue;
-    cell_of(xx, a, w0, ncell, n);
-    const long rr = (n + 16 * CH - 1) / (16 * CH);
+    c = cell_of(off, win, xx, step);
+    const long rr = (c.n + 16 * CH - 1) / (16 * CH);
     for (long rd = 0; rd < rr; ++rd)
-      xcd_round<R, CH, ATOM>(rows, cols, vals, a, w0, ncell, n, rd, sR, sC, sV, W, ldw, H, ldh, lr, lam);
+      xcd_round<R, CH, ATOM>(rows, cols, vals, c.a, c.w0, c.ncell, c.n, rd, sR, sC, sV, W, ldw, H, ldh, lr, lam);
     if (threadIdx.x == 0 && rr > 0) __hip_atomic_fetch_add(ws + 9, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
@@ -659,8 +667,6 @@ __global__ __launch_bounds__(256) void mf_sgd_xcd_flow_kernel(const int* __restr
   int* err = ws + 202;
   const int x = blockIdx.x % XCDS;
   const int nxt = (x + 1) % XCDS;
-  const int sl = threadIdx.x & 15;
-  const int sub = threadIdx.x >> 4;
   // the visibility argument above needs all blocks of one residue b mod 8 to RUN on one
   // XCD, and the 8 residues on 8 different XCDs (the round-robin dispatch of a single-
   // partition device; which physical XCD serves a residue does not matter -- measured: the
@@ -668,7 +674,7 @@ __global__ __launch_bounds__(256) void mf_sgd_xcd_flow_kernel(const int* __restr
   // records its XCC id; a block of x on another XCC, or two residues on one XCC, raise the
   // error word (2) and the host refuses the pass (ops.mf.check_flow_errors)
   if (threadIdx.x == 0) {
-    const int hw = (__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 0xf) + 1;  // HW_REG_XCC_ID
+    const int hw = hw_xcc_id() + 1;
     const int prev = cas_zero(xccmap + x, hw);
     if (prev != 0 && prev != hw) __hip_atomic_store(err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int bit = 1 << (hw - 1);
@@ -677,12 +683,8 @@ __global__ __launch_bounds__(256) void mf_sgd_xcd_flow_kernel(const int* __restr
     if (prev == 0 && (seen & bit)) __hip_atomic_store(err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   for (int step = 0; step < steps; ++step) {
-    const int cell = x * XCDS + (x + step) % XCDS;
-    const long a = off[cell];
-    const long ncell = off[cell + 1] - a;
-    const long w0 = win ? win[cell] : 0;
-    const long n = win ? win[XCDS * XCDS + cell] : ncell;
-    const long nst = (n + CH - 1) / CH;
+    const Cell c = cell_of(off, win, x, step);
+    const long nst = (c.n + CH - 1) / CH;
     const int rounds = (int)((nst + 15) / 16);
     if (rounds == 0) {  // empty cell: complete at once (idempotent)
       if (threadIdx.x == 0) publish(fin + x * XCDS + step);
@@ -713,21 +715,8 @@ __global__ __launch_bounds__(256) void mf_sgd_xcd_flow_kernel(const int* __restr
         __syncthreads();
         __atomic_signal_fence(__ATOMIC_SEQ_CST);
       }
-      const long r0 = (long)rd * 16 * CH;
-      for (int k = threadIdx.x; k < 16 * CH; k += 256) {
-        if (r0 + k < n) {
-          long q = w0 + r0 + k;
-          if (q >= ncell) q -= ncell;
-          sR[k] = rows[a + q];
-          sC[k] = cols[a + q];
-          sV[k] = vals[a + q];
-        }
-      }
-      __syncthreads();
-      const long left = n - (r0 + (long)sub * CH);
-      if (left > 0)
-        sgd_stream_lds<R, true>(sR + sub * CH, sC + sub * CH, sV + sub * CH, left < CH ? (int)left : CH, sl, W,
-                                (unsigned)ldw, H, (unsigned)ldh, lr, lam);
+      xcd_round<R, CH, 0, true, false>(rows, cols, vals, c.a, c.w0, c.ncell, c.n, rd, sR, sC, sV, W, ldw, H, ldh, lr,
+                                       lam);
       __syncthreads();  // the LDS triples are free
       ++mine;
     }
@@ -748,15 +737,6 @@ __global__ __launch_bounds__(256) void mf_sgd_xcd_flow_kernel(const int* __restr
       for (int k = 0; k < 202; ++k) __hip_atomic_store(ws + k, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-}
-
-template <int R, int CH>
-int launch_sgd_xcd_flow(const int* rows, const int* cols, const float* vals, const long* off, const long* win,
-                        int steps, int blocks_per_xcd, float* W, int ldw, float* H, int ldh, float lr, float lam,
-                        int* ws, hipStream_t s) {
-  mf_sgd_xcd_flow_kernel<R, CH><<<dim3((unsigned)(blocks_per_xcd * XCDS)), dim3(256), 0, s>>>(
-      rows, cols, vals, off, win, steps, W, ldw, H, ldh, lr, lam, ws);
-  return harp_launch_status();
 }
 
 template <int R>
@@ -787,6 +767,67 @@ __global__ __launch_bounds__(256) void mf_rmse_kernel(const int* __restrict__ ro
   if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
+// ---- host side: run-time rank / chunk / write-back mode -> template instantiation. Each
+// dispatcher calls the generic lambda `f` with the matching integral_constant tag (its value:
+// decltype(tag)::value), or returns the error of a value that has no kernel.
+template <int N>
+using Int = std::integral_constant<int, N>;
+
+template <class F>
+int dispatch_rank(int r, F&& f) {
+  switch (r) {
+    case 16: return f(Int<16>{});
+    case 32: return f(Int<32>{});
+    case 48: return f(Int<48>{});
+    case 64: return f(Int<64>{});
+    case 128: return f(Int<128>{});
+    case 256: return f(Int<256>{});
+    default: return HARP_EUNSUPPORTED;
+  }
+}
+
+// ratings per stream and round; MIN = 32: the wide kernels, which are not built for 8 / 16
+template <int MIN = 8, class F>
+int dispatch_chunk(int chunk, F&& f) {
+  if constexpr (MIN <= 8) {
+    if (chunk == 8) return f(Int<8>{});
+    if (chunk == 16) return f(Int<16>{});
+  }
+  switch (chunk) {
+    case 32: return f(Int<32>{});
+    case 64: return f(Int<64>{});
+    case 128: return f(Int<128>{});
+    default: return HARP_EBADARG;
+  }
+}
+
+// ATOM write-back mode of sgd_stream_lds. KNOWN DEFECT, kept as is: 6 and 7 (hot H together
+// with H) silently run as mode 0 instead of being rejected or mapped to 2 / 3.
+template <class F>
+int dispatch_atom(int atom, F&& f) {
+  switch (atom) {
+    case 1: return f(Int<1>{});
+    case 2: return f(Int<2>{});
+    case 3: return f(Int<3>{});
+    case 4: return f(Int<4>{});
+    case 5: return f(Int<5>{});
+    default: return f(Int<0>{});
+  }
+}
+
+// what every XCD-blocked launch takes: the cell-major ratings, their cell offsets and
+// optional windows, the factors and the step sizes
+struct XcdArgs {
+  const int *rows, *cols;
+  const float* vals;
+  const long *off, *win;
+  float* W;
+  int ldw;
+  float* H;
+  int ldh;
+  float lr, lam;
+};
+
 template <int R>
 int launch_sgd(const int* rows, const int* cols, const float* vals, long n, int chunk, float* W, int ldw, float* H,
                int ldh, float lr, float lam, hipStream_t s) {
@@ -801,44 +842,22 @@ constexpr int kAtomBits = 28;  // variant bits 2..4: ATOM write-back mode (sgd_s
 
 // variant 0: blockIdx-placed sub-steps (+ placement check when chk != NULL; `gen` is the
 // first launch's generation, one per sub-step); 2: mf_sgd_xcd_placed_kernel (pws)
-template <int R, int CH>
-int launch_sgd_xcd(const int* rows, const int* cols, const float* vals, const long* off, const long* win, int steps,
-                   int blocks_per_xcd, float* W, int ldw, float* H, int ldh, float lr, float lam, int variant,
-                   unsigned long long* chk, unsigned long long gen, int* pws, hipStream_t s) {
-  const dim3 grid((unsigned)(blocks_per_xcd * XCDS));
-  const int atom = (variant >> 2) & 7;
+template <int R, int CH, int ATOM>
+int launch_sgd_xcd(XcdArgs a, int steps, dim3 grid, int variant, unsigned long long* chk,
+                   unsigned long long gen, int* pws, hipStream_t s) {
   const bool placed = (variant & 3) == 2;
   for (int step = 0; step < steps; ++step) {
-    const unsigned long long g = gen + (unsigned long long)step;
-#define XCD_LAUNCH(A)                                                                                        \
-  do {                                                                                                       \
-    if (placed)                                                                                              \
-      mf_sgd_xcd_placed_kernel<R, CH, A><<<grid, dim3(256), 0, s>>>(rows, cols, vals, off, win, step, W, ldw, H, \
-                                                                    ldh, lr, lam, pws);                        \
-    else                                                                                                     \
-      mf_sgd_xcd_kernel<R, CH, A><<<grid, dim3(256), 0, s>>>(rows, cols, vals, off, win, step, W, ldw, H, ldh,   \
-                                                             lr, lam, chk, g);                                \
-  } while (0)
-    switch (atom) {
-      case 1: XCD_LAUNCH(1); break;
-      case 2: XCD_LAUNCH(2); break;
-      case 3: XCD_LAUNCH(3); break;
-      case 4: XCD_LAUNCH(4); break;
-      case 5: XCD_LAUNCH(5); break;
-      default: XCD_LAUNCH(0); break;
-    }
-#undef XCD_LAUNCH
+    if (placed)
+      mf_sgd_xcd_placed_kernel<R, CH, ATOM><<<grid, dim3(256), 0, s>>>(a.rows, a.cols, a.vals, a.off, a.win, step, a.W,
+                                                                       a.ldw, a.H, a.ldh, a.lr, a.lam, pws);
+    else
+      mf_sgd_xcd_kernel<R, CH, ATOM><<<grid, dim3(256), 0, s>>>(a.rows, a.cols, a.vals, a.off, a.win, step, a.W, a.ldw,
+                                                                a.H, a.ldh, a.lr, a.lam, chk,
+                                                                gen + (unsigned long long)step);
     const int st = harp_launch_status();
     if (st != HARP_OK) return st;
   }
   return HARP_OK;
-}
-
-template <int R>
-int launch_rmse(const int* rows, const int* cols, const float* vals, long n, const float* W, int ldw, const float* H,
-                int ldh, double* partial, int nblocks, hipStream_t s) {
-  mf_rmse_kernel<R><<<dim3(nblocks), dim3(256), 0, s>>>(rows, cols, vals, n, W, ldw, H, ldh, partial);
-  return harp_launch_status();
 }
 
 // ---- wide ranks (256 < R <= 4096, R % 4 == 0; BASELINE #1 runs rank 2000) -------------
@@ -961,17 +980,13 @@ __global__ __launch_bounds__(256) void mf_sgd_xcd_wide_kernel(const int* __restr
   const int x = blockIdx.x % XCDS;
   const long j = blockIdx.x / XCDS;
   const long per_xcd = gridDim.x / XCDS;
-  const int cell = x * XCDS + (x + step) % XCDS;
-  const long a = off[cell];
-  const long ncell = off[cell + 1] - a;
-  const long w0 = win ? win[cell] : 0;
-  const long n = win ? win[XCDS * XCDS + cell] : ncell;
-  const long nst = (n + CH - 1) / CH;
+  const Cell c = cell_of(off, win, x, step);
+  const long nst = (c.n + CH - 1) / CH;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   for (long st = j * 4 + wv; st < nst; st += per_xcd * 4) {
     const long i0 = st * CH;
-    const long i1 = i0 + CH < n ? i0 + CH : n;
-    sgd_stream_wide<Q>(rows, cols, vals, a, w0, ncell, i0, i1, threadIdx.x & 63, R, W, ldw, H, ldh, lr, lam);
+    const long i1 = i0 + CH < c.n ? i0 + CH : c.n;
+    sgd_stream_wide<Q>(rows, cols, vals, c.a, c.w0, c.ncell, i0, i1, threadIdx.x & 63, R, W, ldw, H, ldh, lr, lam);
   }
   placement_check(chk, gen, x);
 }
@@ -1007,13 +1022,15 @@ __global__ __launch_bounds__(256) void mf_rmse_wide_kernel(const int* __restrict
 int wide_q(int r) { return r <= 512 ? 2 : r <= 1024 ? 4 : r <= 2048 ? 8 : 16; }
 bool wide_ok(int r) { return r > 256 && r <= 4096 && r % 4 == 0; }
 
-#define WIDE_DISPATCH(R, CALL)                                                          \
-  switch (wide_q(R)) {                                                                  \
-    case 2: return CALL(2);                                                             \
-    case 4: return CALL(4);                                                             \
-    case 8: return CALL(8);                                                             \
-    default: return CALL(16);                                                           \
+template <class F>
+int dispatch_wide(int r, F&& f) {
+  switch (wide_q(r)) {
+    case 2: return f(Int<2>{});
+    case 4: return f(Int<4>{});
+    case 8: return f(Int<8>{});
+    default: return f(Int<16>{});
   }
+}
 
 template <int Q>
 int launch_sgd_wide(const int* rows, const int* cols, const float* vals, long n, int chunk, int r, float* W, int ldw,
@@ -1025,59 +1042,32 @@ int launch_sgd_wide(const int* rows, const int* cols, const float* vals, long n,
   return harp_launch_status();
 }
 
-template <int Q>
-int launch_sgd_xcd_wide(const int* rows, const int* cols, const float* vals, const long* off, const long* win,
-                        int steps, int chunk, int blocks_per_xcd, int r, float* W, int ldw, float* H, int ldh,
-                        float lr, float lam, unsigned long long* chk, unsigned long long gen0, hipStream_t s) {
+template <int Q, int CH>
+int launch_sgd_xcd_wide(XcdArgs a, int steps, dim3 grid, int r, unsigned long long* chk, unsigned long long gen,
+                        hipStream_t s) {
   for (int step = 0; step < steps; ++step) {
-    const unsigned long long gen = gen0 + (unsigned long long)step;
-    if (chunk == 32)
-      mf_sgd_xcd_wide_kernel<Q, 32><<<dim3((unsigned)(blocks_per_xcd * XCDS)), dim3(256), 0, s>>>(
-          rows, cols, vals, off, win, step, r, W, ldw, H, ldh, lr, lam, chk, gen);
-    else if (chunk == 128)
-      mf_sgd_xcd_wide_kernel<Q, 128><<<dim3((unsigned)(blocks_per_xcd * XCDS)), dim3(256), 0, s>>>(
-          rows, cols, vals, off, win, step, r, W, ldw, H, ldh, lr, lam, chk, gen);
-    else
-      mf_sgd_xcd_wide_kernel<Q, 64><<<dim3((unsigned)(blocks_per_xcd * XCDS)), dim3(256), 0, s>>>(
-          rows, cols, vals, off, win, step, r, W, ldw, H, ldh, lr, lam, chk, gen);
+    mf_sgd_xcd_wide_kernel<Q, CH><<<grid, dim3(256), 0, s>>>(a.rows, a.cols, a.vals, a.off, a.win, step, r, a.W, a.ldw,
+                                                             a.H, a.ldh, a.lr, a.lam, chk,
+                                                             gen + (unsigned long long)step);
     const int st = harp_launch_status();
     if (st != HARP_OK) return st;
   }
   return HARP_OK;
 }
 
-template <int Q>
-int launch_rmse_wide(const int* rows, const int* cols, const float* vals, long n, int r, const float* W, int ldw,
-                     const float* H, int ldh, double* partial, int nblocks, hipStream_t s) {
-  mf_rmse_wide_kernel<Q><<<dim3(nblocks), dim3(256), 0, s>>>(rows, cols, vals, n, r, W, ldw, H, ldh, partial);
-  return harp_launch_status();
-}
-
 }  // namespace
-
-#define MF_DISPATCH(R, CALL)          \
-  switch (R) {                        \
-    case 16: return CALL(16);         \
-    case 32: return CALL(32);         \
-    case 48: return CALL(48);         \
-    case 64: return CALL(64);         \
-    case 128: return CALL(128);       \
-    case 256: return CALL(256);       \
-    default: return HARP_EUNSUPPORTED; \
-  }
 
 HARP_EXPORT int harp_mf_sgd(const int* rows, const int* cols, const float* vals, long n, int r, int chunk, float* W,
                             int ldw, float* H, int ldh, float lr, float lam, hipStream_t s) {
   if (n <= 0) return HARP_OK;
   if (chunk <= 0 || ldw < r || ldh < r) return HARP_EBADARG;
-  if (wide_ok(r)) {
-#define SGDW_CALL(QQ) launch_sgd_wide<QQ>(rows, cols, vals, n, chunk, r, W, ldw, H, ldh, lr, lam, s)
-    WIDE_DISPATCH(r, SGDW_CALL)
-#undef SGDW_CALL
-  }
-#define SGD_CALL(RR) launch_sgd<RR>(rows, cols, vals, n, chunk, W, ldw, H, ldh, lr, lam, s)
-  MF_DISPATCH(r, SGD_CALL)
-#undef SGD_CALL
+  if (wide_ok(r))
+    return dispatch_wide(r, [&](auto q) {
+      return launch_sgd_wide<decltype(q)::value>(rows, cols, vals, n, chunk, r, W, ldw, H, ldh, lr, lam, s);
+    });
+  return dispatch_rank(r, [&](auto rr) {
+    return launch_sgd<decltype(rr)::value>(rows, cols, vals, n, chunk, W, ldw, H, ldh, lr, lam, s);
+  });
 }
 
 HARP_EXPORT int harp_mf_xcds() { return XCDS; }
@@ -1104,25 +1094,24 @@ HARP_EXPORT int harp_mf_sgd_xcd(const int* rows, const int* cols, const float* v
     return HARP_EBADARG;
   if ((chk && gen == 0) || (base_variant == 2 && (!pws || wide_ok(r))) || ((variant & kAtomBits) && wide_ok(r)))
     return HARP_EBADARG;
+  const XcdArgs a{rows, cols, vals, off, win, W, ldw, H, ldh, lr, lam};
+  const dim3 grid((unsigned)(blocks_per_xcd * XCDS));
   if (wide_ok(r)) {  // wide ranks: one wave per stream
     if (chunk != 32 && chunk != 64 && chunk != 128) return HARP_EBADARG;
-#define SGDXW_CALL(QQ) \
-  launch_sgd_xcd_wide<QQ>(rows, cols, vals, off, win, steps, chunk, blocks_per_xcd, r, W, ldw, H, ldh, lr, lam, chk, \
-                          gen, s)
-    WIDE_DISPATCH(r, SGDXW_CALL)
-#undef SGDXW_CALL
+    return dispatch_wide(r, [&](auto q) {
+      return dispatch_chunk<32>(chunk, [&](auto ch) {
+        return launch_sgd_xcd_wide<decltype(q)::value, decltype(ch)::value>(a, steps, grid, r, chk, gen, s);
+      });
+    });
   }
-#define SGDX_ARGS rows, cols, vals, off, win, steps, blocks_per_xcd, W, ldw, H, ldh, lr, lam, variant, chk, gen, pws, s
-#define SGDX_CALL(RR)                                                             \
-  (chunk == 8 ? launch_sgd_xcd<RR, 8>(SGDX_ARGS)                                    \
-   : chunk == 16 ? launch_sgd_xcd<RR, 16>(SGDX_ARGS)                                \
-   : chunk == 32 ? launch_sgd_xcd<RR, 32>(SGDX_ARGS)                                \
-   : chunk == 64 ? launch_sgd_xcd<RR, 64>(SGDX_ARGS)                                \
-   : chunk == 128 ? launch_sgd_xcd<RR, 128>(SGDX_ARGS)                              \
-                  : HARP_EBADARG)
-  MF_DISPATCH(r, SGDX_CALL)
-#undef SGDX_CALL
-#undef SGDX_ARGS
+  return dispatch_rank(r, [&](auto rr) {
+    return dispatch_chunk(chunk, [&](auto ch) {
+      return dispatch_atom((variant & kAtomBits) >> 2, [&](auto at) {
+        return launch_sgd_xcd<decltype(rr)::value, decltype(ch)::value, decltype(at)::value>(a, steps, grid, variant,
+                                                                                             chk, gen, pws, s);
+      });
+    });
+  });
 }
 
 // One launch for all `steps` sub-steps (mf_sgd_xcd_flow_kernel); same arguments as
@@ -1136,17 +1125,14 @@ HARP_EXPORT int harp_mf_sgd_xcd_flow(const int* rows, const int* cols, const flo
                                      int ldw, float* H, int ldh, float lr, float lam, int* ws, hipStream_t s) {
   if (blocks_per_xcd <= 0 || steps <= 0 || steps > XCDS || ldw < r || ldh < r || wide_ok(r) || !ws)
     return HARP_EBADARG;
-#define SGDF_ARGS rows, cols, vals, off, win, steps, blocks_per_xcd, W, ldw, H, ldh, lr, lam, ws, s
-#define SGDF_CALL(RR)                                                                  \
-  (chunk == 8 ? launch_sgd_xcd_flow<RR, 8>(SGDF_ARGS)                                   \
-   : chunk == 16 ? launch_sgd_xcd_flow<RR, 16>(SGDF_ARGS)                               \
-   : chunk == 32 ? launch_sgd_xcd_flow<RR, 32>(SGDF_ARGS)                               \
-   : chunk == 64 ? launch_sgd_xcd_flow<RR, 64>(SGDF_ARGS)                               \
-   : chunk == 128 ? launch_sgd_xcd_flow<RR, 128>(SGDF_ARGS)                             \
-                  : HARP_EBADARG)
-  MF_DISPATCH(r, SGDF_CALL)
-#undef SGDF_CALL
-#undef SGDF_ARGS
+  return dispatch_rank(r, [&](auto rr) {
+    return dispatch_chunk(chunk, [&](auto ch) {
+      mf_sgd_xcd_flow_kernel<decltype(rr)::value, decltype(ch)::value>
+          <<<dim3((unsigned)(blocks_per_xcd * XCDS)), dim3(256), 0, s>>>(rows, cols, vals, off, win, steps, W, ldw, H,
+                                                                         ldh, lr, lam, ws);
+      return harp_launch_status();
+    });
+  });
 }
 
 HARP_EXPORT int harp_mf_rmse_blocks() { return 1024; }
@@ -1154,12 +1140,15 @@ HARP_EXPORT int harp_mf_rmse_blocks() { return 1024; }
 HARP_EXPORT int harp_mf_rmse(const int* rows, const int* cols, const float* vals, long n, int r, const float* W, int ldw,
                              const float* H, int ldh, double* partial, hipStream_t s) {
   if (n <= 0) return HARP_OK;
-  if (wide_ok(r)) {
-#define RMSEW_CALL(QQ) launch_rmse_wide<QQ>(rows, cols, vals, n, r, W, ldw, H, ldh, partial, 1024, s)
-    WIDE_DISPATCH(r, RMSEW_CALL)
-#undef RMSEW_CALL
-  }
-#define RMSE_CALL(RR) launch_rmse<RR>(rows, cols, vals, n, W, ldw, H, ldh, partial, 1024, s)
-  MF_DISPATCH(r, RMSE_CALL)
-#undef RMSE_CALL
+  const dim3 grid(1024);  // harp_mf_rmse_blocks()
+  if (wide_ok(r))
+    return dispatch_wide(r, [&](auto q) {
+      mf_rmse_wide_kernel<decltype(q)::value>
+          <<<grid, dim3(256), 0, s>>>(rows, cols, vals, n, r, W, ldw, H, ldh, partial);
+      return harp_launch_status();
+    });
+  return dispatch_rank(r, [&](auto rr) {
+    mf_rmse_kernel<decltype(rr)::value><<<grid, dim3(256), 0, s>>>(rows, cols, vals, n, W, ldw, H, ldh, partial);
+    return harp_launch_status();
+  });
 }
