@@ -79,7 +79,7 @@ EXTRA = {  # named-only flags
     "sgd": [("num_users", int, 0), ("num_items", int, 0)],
     "ccd": [("num_users", int, 0), ("num_items", int, 0)],
     "daal": [("k", int, 0), ("method", str, ""), ("label_cols", int, 1), ("n_trees", int, 50), ("max_depth", int, 10),
-             ("engine", str, "native")],
+             ("engine", str, "native"), ("format", str, "dense"), ("labels", str, "")],
     "mds": [("work_dir", str, "harp-work/mds"), ("checkpoint_every", int, 0)],
 }
 
@@ -411,13 +411,15 @@ def _run_daal(comm, cfg):
     from .models import stats as ST
     from .utils.datasets import load_dense_csv
 
-    import numpy as np
-
     files = _my_files(comm, cfg["input_dir"])
-    A = torch.cat([load_dense_csv(f) for f in files]) if files else torch.zeros((0, 0), dtype=torch.float64)
     algo = cfg["algo"]
     lc = cfg["label_cols"]
     out: Dict[str, Any] = {}
+    if cfg["format"] == "csr":
+        return _save_daal(comm, cfg, _run_daal_csr(comm, cfg, files))
+    if cfg["format"] != "dense":
+        raise ValueError(f"format={cfg['format']!r}: expected 'dense' or 'csr'")
+    A = torch.cat([load_dense_csv(f) for f in files]) if files else torch.zeros((0, 0), dtype=torch.float64)
     if algo in ("cov", "covariance"):
         out = ST.covariance(A, comm)
     elif algo in ("mom", "moments"):
@@ -459,6 +461,55 @@ def _run_daal(comm, cfg):
                "values": torch.cat([t.value for t in forest.trees]), "n_trees": len(forest.trees)}
     else:
         raise ValueError(f"unknown daal algo {algo}")
+    return _save_daal(comm, cfg, out)
+
+
+def _run_daal_csr(comm, cfg, files):
+    """``format=csr``: DAAL CSR text files (three lines: row offsets, columns, values), never
+    densified. The files of the reference's fixtures differ in width (each ends at its own
+    largest column), so the workers agree on the column count first. ``labels`` (algo
+    ``naive``): a file or directory of one-column label files, paired with the input files
+    in sorted order."""
+    from .models import naive_bayes as NB
+    from .models import stats as ST
+    from .utils.datasets import load_daal_csr, load_dense_csv
+
+    algo = cfg["algo"]
+    blocks = [load_daal_csr(f) for f in files]
+    d = _allmax(comm, max((b.shape[1] for b in blocks), default=0))
+    rp, off = [torch.zeros(1, dtype=torch.long)], 0
+    for b in blocks:
+        rp.append(b.crow_indices()[1:] + off)
+        off += b.values().numel()
+    cat = (lambda xs, dt: torch.cat(xs) if xs else torch.zeros(0, dtype=dt))
+    rowptr = torch.cat(rp)
+    A = torch.sparse_csr_tensor(rowptr, cat([b.col_indices() for b in blocks], torch.long),
+                                cat([b.values() for b in blocks], torch.float64), size=(rowptr.numel() - 1, d))
+    if algo in ("cov", "covariance"):
+        return ST.covariance(A, comm)
+    if algo in ("mom", "moments"):
+        return ST.low_order_moments(A, comm)
+    if algo == "pca":
+        return ST.pca(A, comm, cfg["method"] or "correlation")
+    if algo in ("naive", "nb"):
+        if not cfg["labels"]:
+            raise ValueError("algo=naive with format=csr needs --labels")
+        pair = dict(zip(sorted(_files(cfg["input_dir"])), sorted(_files(cfg["labels"]))))
+        y = (torch.cat([load_dense_csv(pair[f]).reshape(-1) for f in files]).long() if files
+             else torch.zeros(0, dtype=torch.long))
+        return NB.train(A, y, cfg["k"] or _allmax(comm, int(y.max()) + 1 if y.numel() else 0), comm)
+    if algo == "kmeans":
+        from .models.kmeans_csr import kmeans_init, kmeans_sparse
+
+        C0 = kmeans_init(A, cfg["k"] or 10, comm, method=cfg["method"] or "first")
+        return kmeans_sparse(A, C0, cfg["iterations"], comm)
+    raise ValueError(f"daal algo {algo} has no csr variant")
+
+
+def _save_daal(comm, cfg, out):
+    import numpy as np
+
+    algo = cfg["algo"]
     if comm.rank == 0:
         os.makedirs(cfg["work_dir"], exist_ok=True)
         for k, v in (out.items() if isinstance(out, dict) else []):

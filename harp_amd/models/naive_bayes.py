@@ -4,7 +4,8 @@ Reference: ml/daal/.../daal_naive/{dense,csr}distri (multinomial_naive_bayes ste
 every worker -> gather -> step2 master; NaiveDaalCollectiveMapper.java). Partial result =
 per-class feature sums + per-class counts. Here the per-class sums are one
 (one-hot)^T X GEMM on the device; one allreduce merges the partials; every worker holds
-the model. Prediction is X log(theta)^T (+ log prior): a GEMM + argmax.
+the model. Prediction is X log(theta)^T (+ log prior): a GEMM + argmax. CSR / COO input is
+never densified: the sums and the fused product + argmax come from ``ops.csr_stats`` in fp64.
 """
 from __future__ import annotations
 
@@ -12,8 +13,8 @@ from typing import Dict, Optional
 
 import torch
 
+from ..ops import csr_stats as CS
 from ..ops import linalg as LA
-
 from ..parallel.comm import Communicator
 from .common import reduce_partials
 from .stats import _local
@@ -28,15 +29,12 @@ def train(X: torch.Tensor, y: torch.Tensor, num_classes: int, comm: Optional[Com
     comm = _local(comm)
     yl = y.reshape(-1).long().to(X.device)
     acc = torch.float64 if X.device.type == "cpu" else torch.float32
-    if X.is_sparse or X.layout == torch.sparse_csr:
-        Xc = X.to_sparse_coo().coalesce()
-        rows, cols = Xc.indices()
-        sums = torch.zeros((num_classes, X.shape[1]), dtype=acc, device=X.device)
-        sums.index_put_((yl[rows], cols), Xc.values().to(acc), accumulate=True)
+    if LA._is_sparse(X):
+        sums, counts = CS.class_sums(CS.to_csr_operand(X), yl, num_classes)  # fp64, from the CSR arrays
     else:
         onehot = torch.nn.functional.one_hot(yl, num_classes).to(acc)
         sums = LA.atb(onehot, X.to(acc))
-    counts = torch.bincount(yl, minlength=num_classes).to(acc)
+        counts = torch.bincount(yl, minlength=num_classes).to(acc)
     p = reduce_partials(comm, {"sums": sums, "counts": counts})
     fs = p["sums"] + alpha
     log_theta = (fs / fs.sum(1, keepdim=True)).log()
@@ -49,6 +47,8 @@ def train(X: torch.Tensor, y: torch.Tensor, num_classes: int, comm: Optional[Com
 
 
 def predict(X: torch.Tensor, model: Dict[str, torch.Tensor]) -> torch.Tensor:
+    if LA._is_sparse(X):  # argmax fused into the sparse product: no [n, C] scores, no dense X
+        return CS.spmm(CS.to_csr_operand(X), model["logTheta"].to(X.device).t(), model["logPrior"], argmax=True)
     lt = model["logTheta"].to(X.device)
     Xd = _dense(X).to(lt.dtype)
     return (Xd @ lt.t() + model["logPrior"].to(X.device)).argmax(1)

@@ -92,10 +92,13 @@ def covariance_partial(X, dtype: Optional[str] = None) -> Dict[str, torch.Tensor
         n, s, G = LA.gram_stats(X)
         return {"n": n.reshape(1).double(), "sum": s.double(), "xtx": G.double()}
     if LA._is_sparse(X):
-        n = X.shape[0]
-        s = LA.colsum(X)
-        return {"n": torch.tensor([float(n)], dtype=torch.float64, device=s.device), "sum": s.double(),
-                "xtx": LA.gram(X).double()}
+        # one operand build; n, the sums and X^T X all come from it, in fp64, never densified
+        from ..ops import csr_stats as CS
+
+        A = CS.to_csr_operand(X)
+        s = CS.col_moments(A)["sum"]
+        return {"n": torch.tensor([float(A.n)], dtype=torch.float64, device=s.device), "sum": s,
+                "xtx": LA.symmetrize_upper(CS.gram(A))}
     if mode == "bf16":
         if X.device.type == "cuda" and LA._has_syrk() and _native(X):
             return covariance_partial(LA.FeatureMajor.from_rows(X), "bf16")
@@ -156,7 +159,9 @@ def low_order_moments(X: torch.Tensor, comm: Optional[Communicator] = None,
     :func:`covariance`: "bf16" sums the bf16-rounded operands in fp32, "fp32" / "fp64" sum
     shifted row slices and accumulate in fp64 (sumSquaresCentered then has no cancellation)."""
     comm = _local(comm)
-    Xd = X.to_dense() if X.is_sparse or X.layout == torch.sparse_csr else X
+    if LA._is_sparse(X):
+        return _low_order_moments_csr(X, comm)
+    Xd = X
     mode = _policy(Xd, dtype)
     n = float(Xd.shape[0])
     if mode == "bf16":
@@ -189,6 +194,34 @@ def low_order_moments(X: torch.Tensor, comm: Optional[Communicator] = None,
     Xm = Xd.double() if Xd.device.type == "cpu" else Xd.float()
     mm = reduce_partials(comm, {"min": Xm.min(0).values.double(), "negmax": -Xm.max(0).values.double()},
                          Operation.MIN, dtype=torch.float64)
+    var = ss / max(N - 1, 1)
+    sd = var.clamp_min(0).sqrt()
+    return {"minimum": mm["min"], "maximum": -mm["negmax"], "sum": sums["sum"], "sumSquares": sums["sumsq"],
+            "sumSquaresCentered": ss, "mean": mean, "secondOrderRawMoment": sums["sumsq"] / N, "variance": var,
+            "standardDeviation": sd, "variation": sd / mean}
+
+
+def _low_order_moments_csr(X, comm: Communicator) -> Dict[str, torch.Tensor]:
+    """Sparse branch of :func:`low_order_moments`, fp64, from the stored entries only
+    (``ops.csr_stats``): a raw pass (sum, sumSquares, minimum, maximum), a second pass
+    centred on this rank's column mean (its centred sum of squares, no cancellation), the
+    implicit zeros added in closed form, then the same between-rank combination."""
+    from ..ops import csr_stats as CS
+
+    A = CS.to_csr_operand(X)
+    n = float(A.n)
+    raw = CS.with_implicit_zeros(CS.col_moments(A), A.n)
+    s1, s2 = raw["sum"], raw["sumsq"]
+    local_mean = s1 / max(n, 1.0)
+    cen = CS.with_implicit_zeros(CS.col_moments(A, local_mean), A.n, local_mean)
+    ss_local = cen["sumsq"] - cen["sum"] * cen["sum"] / max(n, 1.0)
+    sums = reduce_partials(comm, {"n": torch.tensor([n], dtype=torch.float64, device=s1.device), "sum": s1,
+                                  "sumsq": s2}, dtype=torch.float64)
+    N = sums["n"].item()
+    mean = sums["sum"] / N
+    ss = reduce_partials(comm, {"ss": ss_local + n * (local_mean - mean.to(s1.device)) ** 2},
+                         dtype=torch.float64)["ss"]
+    mm = reduce_partials(comm, {"min": raw["min"], "negmax": -raw["max"]}, Operation.MIN, dtype=torch.float64)
     var = ss / max(N - 1, 1)
     sd = var.clamp_min(0).sqrt()
     return {"minimum": mm["min"], "maximum": -mm["negmax"], "sum": sums["sum"], "sumSquares": sums["sumsq"],
@@ -236,6 +269,8 @@ def pca(X, comm: Optional[Communicator] = None, method: str = "correlation",
     elif method == "svd":
         if isinstance(X, LA.FeatureMajor):
             raise ValueError("method='svd' needs the row-major data")
+        if LA._is_sparse(X):
+            raise ValueError("method='svd' needs the dense z-scored rows: use method='correlation' on sparse input")
         mom = low_order_moments(X, comm, dtype=dtype)
         Z = (X.double() - mom["mean"].to(X.device)) / mom["standardDeviation"].to(X.device).clamp_min(1e-300)
         qr = tsqr(Z, comm, want_q=False)

@@ -3,8 +3,9 @@
 ``gram(X)`` = X^T X and ``colsum(X)`` — the step-1 partials of covariance / moments /
 PCA / normal-equation regressions (DAAL ``DistributedStep1Local``). On the GPU, bf16 and
 fp32 inputs go to the hand-written MFMA SYRK kernel in ``csrc/syrk.hip`` (upper-triangle
-tiles only, fp32 accumulation, column sums fused); fp64 and sparse inputs use torch
-(rocBLAS / rocSPARSE) — plain library GEMMs.
+tiles only, fp32 accumulation, column sums fused); fp64 dense inputs use torch (rocBLAS).
+Sparse (CSR / COO) inputs go to ``ops.csr_stats`` in fp64: the native CSR kernels of
+``csrc/csr_stats.hip`` on the GPU, the non-densifying torch reference on the CPU.
 """
 from __future__ import annotations
 
@@ -21,18 +22,19 @@ def _is_sparse(X: torch.Tensor) -> bool:
 
 def colsum(X: torch.Tensor) -> torch.Tensor:
     if _is_sparse(X):
-        Xc = X.to_sparse_coo().coalesce()
-        out = torch.zeros(X.shape[1], dtype=torch.float64, device=X.device)
-        return out.index_add_(0, Xc.indices()[1], Xc.values().double())
+        from . import csr_stats as CS
+
+        return CS.col_moments(CS.to_csr_operand(X))["sum"]
     acc = torch.float64 if X.device.type == "cpu" else torch.float32
     return X.to(acc).sum(0)
 
 
 def gram(X: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-    """X^T X (fp64 on CPU, fp32 accumulation on the GPU)."""
+    """X^T X (fp64 on CPU and for sparse input, fp32 accumulation of dense input on the GPU)."""
     if _is_sparse(X):
-        Xc = X.to_sparse_csr().to(torch.float64 if X.device.type == "cpu" else torch.float32)
-        G = (Xc.t() @ Xc.to_dense()) if X.device.type != "cpu" else (Xc.to_dense().t() @ Xc.to_dense())
+        from . import csr_stats as CS
+
+        G = symmetrize_upper(CS.gram(CS.to_csr_operand(X)))
         return G if out is None else out.add_(G)
     if X.device.type == "cpu":
         Xd = X.double()
