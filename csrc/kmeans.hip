@@ -19,10 +19,10 @@
 //    The within-tile register index is packed into the 4 low mantissa bits of the
 //    distance (relative perturbation 2^-19, far below the bf16 operand rounding).
 //  * X fragments stay in VGPRs for the whole centroid sweep; centroid tiles stream
-//    through double-buffered LDS filled by global_load_lds (LDS-DMA, no staging VGPRs)
-//    with a per-row chunk rotation applied to the DMA source so ds_read_b128 stays
-//    conflict-free; A fragments are register double-buffered across 32-row groups; one
-//    barrier per stage.
+//    through double-buffered LDS (three slots in the keyless sweep) filled by
+//    global_load_lds (LDS-DMA, no staging VGPRs) with a per-row chunk rotation applied to
+//    the DMA source so ds_read_b128 stays conflict-free; A fragments are register
+//    double-buffered across 32-row groups; one barrier per stage.
 //  * column d of X (1.0) meets column d of -2C (0): the accumulation adds (x, 1) =
 //    (partial sum, count) in one row: the Harp centroid row layout (sum + count) falls out
 //    of the data layout.
@@ -75,13 +75,30 @@ __device__ __forceinline__ void stage_dma(const __bf16* __restrict__ cm2, int ti
   }
 }
 
-template <int KS, int G, int WAVES, int RG, int PIPE, int PRIO = 0, int KEYLESS = 0>
+// half H (0: waves 0 .. WAVES/2-1, 1: the rest) requests piece round p of the tile two stages
+// ahead behind the first MFMAs of the chain issued in item i of the ring sweep, -1 for none:
+// all of them behind the barrier in item 3 and inside the same stage. The two waves of a SIMD
+// (w and w + WAVES/2) are in different halves, so they never request in the same item. (The
+// chains issued in items 2, 6, 10, 14 carry the A-fragment reads; 6, 10 and 14 hold a request
+// of one half as well, which was measured as it stands and not moved.)
+constexpr int km_ring_piece_at(int H, int i) {
+  constexpr int at[2][4] = {{5, 7, 10, 13}, {6, 9, 11, 14}};
+  for (int p = 0; p < 4; ++p)
+    if (at[H][p] == i) return p;
+  return -1;
+}
+constexpr int KM_RING_BARRIER_ITEM = 3;
+
+template <int KS, int G, int WAVES, int RG, int PIPE, int PRIO = 0, int KEYLESS = 0, int RING = 0>
 __global__ __launch_bounds__(WAVES * 64) void kmeans_assign_kernel(
     const __bf16* __restrict__ X, long ldx, const __bf16* __restrict__ Cm2, long N, int ntiles, int tail_rg,
     int dcount, int* __restrict__ labels, float* __restrict__ sums, int ld_sums, float* __restrict__ obj_partial,
     float* __restrict__ mind) {
   using C = KMCfg<KS, G, WAVES, RG>;
-  __shared__ __attribute__((aligned(16))) char smem[2 * C::TILE_BYTES + WAVES * 4];
+  constexpr int NSLOT = RING ? 3 : 2;  // LDS slots of one centroid tile each
+  static_assert(!RING || (KEYLESS && PIPE > 0 && G == 4 && RG == 4 && WAVES == 8 && KS <= 8),
+                "the ring sweep is written for the keyless 4 x 4-item stage of 8 waves");
+  __shared__ __attribute__((aligned(16))) char smem[NSLOT * C::TILE_BYTES + WAVES * 4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
   const int srot = (r >> 3) & 1;
@@ -93,6 +110,9 @@ __global__ __launch_bounds__(WAVES * 64) void kmeans_assign_kernel(
     if (__builtin_amdgcn_readfirstlane(tid) >= WAVES * 32) __builtin_amdgcn_s_setprio(1);
   // kick off the first centroid tile before loading this wave's points
   stage_dma<C>(Cm2, 0, smem, wave, lane);
+  // ring: the second tile too (with one tile, that tile again: slot 1 is then never used, but
+  // the chain the last stage starts for a stage that does not exist reads written memory)
+  if constexpr (RING) stage_dma<C>(Cm2, ntiles > 1 ? 1 : 0, smem + C::TILE_BYTES, wave, lane);
 
   // ---- this wave's points: B-operand fragments, resident for the whole sweep
   bf16x8 xf[G][KS];
@@ -148,6 +168,131 @@ __global__ __launch_bounds__(WAVES * 64) void kmeans_assign_kernel(
 
   // full tiles; a last tile of only tail_rg (< RG) row groups runs after the loop
   const int nfull = tail_rg ? ntiles - 1 : ntiles;
+  if constexpr (RING) {
+    // The ring sweep (variant 16): the item pipeline of the two-slot body below run as ONE
+    // stream over all full stages, with nothing at a stage edge that is not also inside a stage.
+    //  * Three LDS slots, tile t in slot t % 3. One barrier per stage, at item 3. In front of it
+    //    a wave waits for its own pieces of tile t + 1 (requested during stage t - 1; tiles 0
+    //    and 1 in the prologue), so behind the barrier of stage t
+    //      - tile t + 1 is visible to every wave: its first read is at item 14 of stage t;
+    //      - every wave has left stage t - 1 (it passed that stage's item 15 to get here; the
+    //        stage's last read of its own slot is at item 10), so slot (t - 1) % 3 = (t + 2) % 3
+    //        is free:
+    //        the pieces of tile t + 2 go there, one per item, behind that barrier and in front
+    //        of the barrier of stage t + 1, which orders them against their first read.
+    //    Past the last tile the request repeats the last tile, into a slot nothing reads again
+    //    (the two live slots are t % 3 and (t + 1) % 3): no branch inside the item stream.
+    //  * Row group 0 of stage t + 1 is read under the last chain of stage t like any next row
+    //    group, and the chain of (stage t + 1, item 0) stands in front of the epilogue of
+    //    (stage t, item 15): accumulator and A fragments are carried over the loop edge. The
+    //    last stage starts such a chain for a stage that is not there (a tail tile's first
+    //    items, or a copy of the last tile); its result is dropped, so the one drain is at
+    //    the end of the sweep, in front of the tail tile.
+    //  * Address registers: two carried per-lane LDS bases and immediate ds_read offsets
+    //    (aoff[s] = aoff[0] + 32 s except the last chunk of the rotated rows, which wraps: the
+    //    second base), a scalar tile pointer plus one 32-bit lane offset per piece, scalar LDS
+    //    destinations.
+    //  * Every item is fenced (r9's hand-over: five MFMAs of chain i + 1, a hard fence, then
+    //    epilogue i over the rest): unfenced, hipcc reads the next row group's fragments in
+    //    front of the chain that still uses their registers and the 7 k-step instance spills.
+    // The k order of a chain and the group order of the min chain are the two-slot body's: labels
+    // are bit-identical (profiles/r10_sweep_ring).
+    constexpr int NI = RG * G, RGB = 32 * C::CPR * 16, HALF = WAVES / 2, HEAD = KS < 5 ? KS : 5;
+    const int swave = __builtin_amdgcn_readfirstlane(wave);
+    unsigned loff[4];  // byte offset of this lane's 16 B inside a tile, per piece round
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int q = (p * WAVES + wave) * 64 + lane;
+      const int row = q / C::CPR;
+      int c = q - row * C::CPR - ((row >> 3) & 1);
+      if (c < 0) c += C::CPR;
+      loff[p] = (unsigned)(row * C::CPR + c) * 16u;
+    }
+    auto sweep = [&](auto htag) {
+      constexpr int H = decltype(htag)::value;
+      int cur = 0, nxt = C::TILE_BYTES, nn = 2 * C::TILE_BYTES;  // slot byte offsets
+      // the lane's LDS read bases, carried: they move to the next slot in front of the reads
+      // of item 14 (an add of a scalar), the row group inside the slot is an immediate offset
+      int ab = aoff[0], abL = aoff[KS - 1] - 32 * (KS - 1);
+      auto a_read = [&](int imm, int s) { return *(const bf16x8*)(smem + (s == KS - 1 ? abL : ab) + (imm + 32 * s)); };
+      bf16x8 af[2][KS];
+      floatx16 acc[2];
+      // k-steps s0 .. s1 - 1 of item j's chain into acc[j & 1]. Under the last point group of a
+      // row group each A fragment of the next row group (of the next stage's first, from the
+      // next slot) is read right behind the MFMA of the same k-step: pinned there by the
+      // fences below the fragments need no third buffer
+      auto chain = [&](int j, int s0, int s1) {
+        const int rgj = j / G, gj = j % G;
+        floatx16& a = acc[j & 1];
+        if (s0 == 0) {
+#pragma unroll
+          for (int q = 0; q < 16; ++q) a[q] = 0.f;
+          if (gj == G - 1 && rgj + 1 == RG) {
+            ab += nxt - cur;
+            abL += nxt - cur;
+          }
+        }
+#pragma unroll
+        for (int s = s0; s < s1; ++s) {
+          a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[rgj & 1][s], xf[gj][s], a, 0, 0, 0);
+          if (gj == G - 1) af[(rgj + 1) & 1][s] = a_read(rgj + 1 < RG ? (rgj + 1) * RGB : 0, s);
+        }
+      };
+#pragma unroll
+      for (int s = 0; s < KS; ++s) af[0][s] = a_read(0, s);
+      chain(0, 0, KS);
+      __builtin_amdgcn_sched_barrier(0);
+      for (int t = 0; t < nfull; ++t) {
+        const int tq = t + 2 < ntiles ? t + 2 : ntiles - 1;
+        const char* gsrc = (const char*)Cm2 + (size_t)tq * C::TILE_BYTES;
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+          const int rg = i / G, g = i % G;
+          // the first HEAD MFMAs of chain i + 1 stand behind a hard fence, in front of every
+          // VALU of epilogue i: with five in front the hazard wait of the epilogue's head is
+          // out of the stream (profiles/r9_sweep_pipe)
+          chain((i + 1) % NI, 0, HEAD);
+          __builtin_amdgcn_sched_barrier(0);
+          if (i == KM_RING_BARRIER_ITEM) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+          }
+          constexpr int NP = (C::DMA_INSTR - H * HALF + WAVES - 1) / WAVES;  // piece rounds of this half
+          const int p = km_ring_piece_at(H, i);
+          if (p >= 0 && p < NP) {
+            // the empty asm keeps the zero-extension of the lane offset beside the load, where
+            // it folds into the scalar-base address form (hoisted out of the loop it becomes
+            // a 64-bit register pair and an add per piece)
+            unsigned lo = loff[p];
+            asm("" : "+v"(lo));
+            __builtin_amdgcn_global_load_lds(
+                (const void __attribute__((address_space(1)))*)(gsrc + (size_t)lo),
+                (void __attribute__((address_space(3)))*)(smem + nn + (p * WAVES + swave) * 1024), 16, 0, 0);
+          }
+          chain((i + 1) % NI, HEAD, KS);
+          tile_argmin(acc[i & 1], g, t * RG + rg);
+          // epilogue i (10 VALU) over the rest of chain i + 1, then a second fence
+          __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+#pragma unroll
+          for (int s = HEAD; s < KS; ++s) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        const int o = cur;
+        cur = nxt;
+        nxt = nn;
+        nn = o;
+      }
+    };
+    if (nfull > 0) {
+      if (swave < HALF) sweep(std::integral_constant<int, 0>{});
+      else sweep(std::integral_constant<int, 1>{});
+    }
+    // the last stages' requests: none may land after the workgroup has gone
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  } else
   for (int t = 0; t < nfull; ++t) {
     if (t + 1 < ntiles) stage_dma<C>(Cm2, t + 1, smem + ((t + 1) & 1) * C::TILE_BYTES, wave, lane);
     const char* buf = smem + (t & 1) * C::TILE_BYTES;
@@ -218,7 +363,7 @@ __global__ __launch_bounds__(WAVES * 64) void kmeans_assign_kernel(
     // K not a multiple of the stage: only the live 32-row groups of the last tile (its DMA
     // landed with the previous stage's wait + barrier; the rows past them are never read)
     const int t = ntiles - 1;
-    const char* buf = smem + (t & 1) * C::TILE_BYTES;
+    const char* buf = smem + (t % NSLOT) * C::TILE_BYTES;
     for (int rg = 0; rg < tail_rg; ++rg) {
       const char* nb = buf + rg * 32 * C::CPR * 16;
       bf16x8 af[KS];
@@ -266,13 +411,16 @@ __global__ __launch_bounds__(WAVES * 64) void kmeans_assign_kernel(
     const long p = pbase + g * 32 + r;
     if (h == 0 && p < N) {
       labels[p] = idx;
-      local_obj += fmaxf(bv + xs, 0.f);
-      if (mind) mind[p] = bv + xs;  // squared distance to the chosen centroid (rotation merge)
+      // keyed: the distance without the index bits in its low mantissa (exact where the
+      // products are: those four bits of the candidate were cleared when the index went in)
+      const float bd = KEYLESS ? bv : __uint_as_float(__float_as_uint(bv) & ~0xFu);
+      local_obj += fmaxf(bd + xs, 0.f);
+      if (mind) mind[p] = bd + xs;  // squared distance to the chosen centroid (rotation merge)
     }
   }
   if (obj_partial) {
     local_obj = wave_sum(local_obj);
-    float* red = (float*)(smem + 2 * C::TILE_BYTES);
+    float* red = (float*)(smem + NSLOT * C::TILE_BYTES);
     if (lane == 0) red[wave] = local_obj;
     __syncthreads();
     if (tid == 0) {
@@ -772,19 +920,21 @@ __global__ __launch_bounds__(256) void kmeans_wide_finish_kernel(const unsigned 
   if (threadIdx.x == 0 && obj_partial) obj_partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-template <int KS, int G, int WAVES, int RG, int PIPE = 0, int PRIO = 0, int KEYLESS = 0>
+template <int KS, int G, int WAVES, int RG, int PIPE = 0, int PRIO = 0, int KEYLESS = 0, int RING = 0>
 int launch_assign(const void* X, long ldx, const void* Cm2, long N, int Kp, int d, int* labels, float* sums,
                   int ld_sums, float* obj_partial, float* mind, hipStream_t stream) {
   using C = KMCfg<KS, G, WAVES, RG>;
   if (Kp % 32 || (KEYLESS && sums)) return HARP_EBADARG;  // no fused atomics in the keyless sweep
   const long nblk = (N + C::PTS - 1) / C::PTS;
   const int ntiles = (Kp + C::TILE - 1) / C::TILE, tail_rg = (Kp % C::TILE) / 32;
-  kmeans_assign_kernel<KS, G, WAVES, RG, PIPE, PRIO, KEYLESS><<<dim3((unsigned)nblk), dim3(C::THREADS), 0, stream>>>(
+  // the ring sweep spills at 8 k-steps (660 B): that instance keeps the two-slot body
+  constexpr int RINGK = RING && KS <= 7;
+  kmeans_assign_kernel<KS, G, WAVES, RG, PIPE, PRIO, KEYLESS, RINGK><<<dim3((unsigned)nblk), dim3(C::THREADS), 0, stream>>>(
       (const __bf16*)X, ldx, (const __bf16*)Cm2, N, ntiles, tail_rg, d, labels, sums, ld_sums, obj_partial, mind);
   return harp_launch_status();
 }
 
-// variant -> (G, WAVES, RG, PIPE, PRIO, KEYLESS), the one table both the launch and
+// variant -> (G, WAVES, RG, PIPE, PRIO, KEYLESS, RING), the one table both the launch and
 // harp_kmeans_points_per_block read. Kp (the rows swept) must be a multiple of 32; Cm2 must
 // hold round_up(Kp, 128) rows (the last stage's DMA reads the whole tile).
 // Only the measured frontier ships (profiles/r1_kmeans_*): 15 (= 14 + static priority for the
@@ -792,16 +942,19 @@ int launch_assign(const void* X, long ldx, const void* Cm2, long N, int Kp, int 
 // 4 the one-group shape wide rows (9..16 k-steps) use. 16 is 15 without index keys: it writes
 // the winning 32-row group id (0 .. Kp / 32 - 1) to labels and takes no fused sums; the
 // caller finishes the labels with harp_kmeans_resolve_rowsum (kmeans_resolve.hip). The
-// default for rows of <= 128 padded columns with bucketed sums (profiles/r7_keyless).
-#define KM_VARIANT_TABLE(ROW, KS) \
-  ROW(KS, 4, 1, 16, 2, 0, 0, 0)   \
-  ROW(KS, 13, 4, 8, 2, 2, 0, 0)   \
-  ROW(KS, 14, 4, 8, 4, 2, 0, 0)   \
-  ROW(KS, 15, 4, 8, 4, 2, 1, 0)   \
-  ROW(KS, 16, 4, 8, 4, 2, 1, 1)
-#define KM_LAUNCH_ROW(KS, V, G, WAVES, RG, PIPE, PRIO, KEYLESS) \
-  case V: return launch_assign<KS, G, WAVES, RG, PIPE, PRIO, KEYLESS>(X, ldx, Cm2, N, Kp, d, labels, sums, ld, op, md, s);
-#define KM_PTS_ROW(KS, V, G, WAVES, RG, PIPE, PRIO, KEYLESS) \
+// default for rows of <= 128 padded columns with bucketed sums (profiles/r7_keyless). Its
+// sweep is the ring form (three LDS slots, the item pipeline carried over the stage edge;
+// profiles/r10_sweep_ring) at 1..7 k-steps; at 8 that form spills, and the instance keeps the
+// two-slot body the keyed variants run.
+#define KM_VARIANT_TABLE(ROW, KS)       \
+  ROW(KS, 4, 1, 16, 2, 0, 0, 0, 0)      \
+  ROW(KS, 13, 4, 8, 2, 2, 0, 0, 0)      \
+  ROW(KS, 14, 4, 8, 4, 2, 0, 0, 0)      \
+  ROW(KS, 15, 4, 8, 4, 2, 1, 0, 0)      \
+  ROW(KS, 16, 4, 8, 4, 2, 1, 1, 1)
+#define KM_LAUNCH_ROW(KS, V, G, WAVES, RG, PIPE, PRIO, KEYLESS, RING) \
+  case V: return launch_assign<KS, G, WAVES, RG, PIPE, PRIO, KEYLESS, RING>(X, ldx, Cm2, N, Kp, d, labels, sums, ld, op, md, s);
+#define KM_PTS_ROW(KS, V, G, WAVES, RG, PIPE, PRIO, KEYLESS, RING) \
   case V: return KMCfg<KS, G, WAVES, RG>::PTS;
 #define KM_VARIANTS(KS)                      \
   switch (variant) {                         \

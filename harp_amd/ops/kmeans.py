@@ -33,7 +33,10 @@ ONES = 4  # X columns d..d+3 hold 1.0
 # sweep finds only the winning 32-row centroid group (no index bits in the distances: 1.6
 # instead of 4.3 VALU instructions per MFMA) and the bucketed gather-sum pass, which reads
 # every row anyway, finds the row inside the group (csrc/kmeans_resolve.hip;
-# profiles/r7_keyless, r9_sweep_pipe). Calls without a bucketed sum to resolve in run 15.
+# profiles/r7_keyless, r9_sweep_pipe). Its sweep runs as one item stream over all stages: three
+# LDS slots, one barrier inside a stage, the next tiles requested one piece per item, nothing
+# drained at a stage edge (1..7 k-steps; profiles/r10_sweep_ring). Calls without a bucketed sum
+# to resolve in run 15.
 DEFAULT_VARIANT = 16
 KEYLESS_VARIANT, KEYED_VARIANT = 16, 15
 KEYLESS_MAX_DP = 128
