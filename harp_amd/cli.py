@@ -23,6 +23,10 @@ same parameters as named flags (which win when both are given):
             (harp-daal-interface data_aux/Initialize.java:97-130 common prefix)
             algo dforest / dforest_reg: decision forest over the workers' row shards (last
             column = label / target)      [--k classes --n-trees --max-depth --engine]
+            algo ar (alias apriori): association rules over ``tid,item`` CSV files; every
+            worker's transactions are its own (tids disjoint between workers' files)
+            (daal_ar/Aprior/ARDaalCollectiveMapper.java)  [--min-support 0.001
+            --min-confidence 0.7 --engine native|torch --k items]
 
 ``maps`` = number of workers. Outside torchrun the CLI spawns ``maps`` local worker
 processes (RCCL on GPUs when ``maps`` <= visible GPUs, else gloo on CPU); under torchrun
@@ -79,7 +83,8 @@ EXTRA = {  # named-only flags
     "sgd": [("num_users", int, 0), ("num_items", int, 0)],
     "ccd": [("num_users", int, 0), ("num_items", int, 0)],
     "daal": [("k", int, 0), ("method", str, ""), ("label_cols", int, 1), ("n_trees", int, 50), ("max_depth", int, 10),
-             ("engine", str, "native"), ("format", str, "dense"), ("labels", str, "")],
+             ("engine", str, "native"), ("format", str, "dense"), ("labels", str, ""),
+             ("min_support", float, 0.001), ("min_confidence", float, 0.7)],
     "mds": [("work_dir", str, "harp-work/mds"), ("checkpoint_every", int, 0)],
 }
 
@@ -415,6 +420,8 @@ def _run_daal(comm, cfg):
     algo = cfg["algo"]
     lc = cfg["label_cols"]
     out: Dict[str, Any] = {}
+    if algo in ("ar", "apriori"):
+        return _save_daal(comm, cfg, _run_daal_ar(comm, cfg, files))
     if cfg["format"] == "csr":
         return _save_daal(comm, cfg, _run_daal_csr(comm, cfg, files))
     if cfg["format"] != "dense":
@@ -462,6 +469,25 @@ def _run_daal(comm, cfg):
     else:
         raise ValueError(f"unknown daal algo {algo}")
     return _save_daal(comm, cfg, out)
+
+
+def _run_daal_ar(comm, cfg, files):
+    """Association rules on ``tid,item`` CSV files (daal_ar, ARDaalCollectiveMapper). Every
+    worker's transactions are its own: the tids of its files are renumbered locally and must
+    not occur in another worker's files, so a transaction may not be split over workers. The
+    item count is agreed on first (largest item id + 1 over all workers, or ``--k``)."""
+    from .models.apriori import apriori_transactions
+    from .utils.datasets import load_dense_csv
+
+    A = (torch.cat([load_dense_csv(f).reshape(-1, 2) for f in files]).long() if files
+         else torch.zeros((0, 2), dtype=torch.long))
+    n_items = cfg["k"] or _allmax(comm, int(A[:, 1].max()) + 1 if A.shape[0] else 0)
+    dev = comm.device if cfg["engine"] == "native" else None
+    res = apriori_transactions(A[:, 0], A[:, 1], n_items, cfg["min_support"], cfg["min_confidence"], comm,
+                               engine=cfg["engine"], device=dev)
+    out = {k: v for k, v in res.items() if isinstance(v, torch.Tensor)}  # the DAAL result tables
+    out.update(n_transactions=res["n_transactions"], n_itemsets=len(res["counts"]), n_rules=len(res["rules"]))
+    return out
 
 
 def _run_daal_csr(comm, cfg, files):
