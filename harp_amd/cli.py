@@ -23,6 +23,11 @@ same parameters as named flags (which win when both are given):
             (harp-daal-interface data_aux/Initialize.java:97-130 common prefix)
             algo dforest / dforest_reg: decision forest over the workers' row shards (last
             column = label / target)      [--k classes --n-trees --max-depth --engine]
+            algo adaboost / logitboost / brownboost / stump: boosted stumps on CSV rows (last
+            column = label; labels -1 / +1 are read as y > 0). adaboost and logitboost train
+            one model over the workers' row shards (native engine) or on the gathered rows
+            (torch engine); brownboost and stump need maps = 1
+            [--rounds 50 --k classes --engine native|torch --c 2.0 (brownboost)]
             algo ar (alias apriori): association rules over ``tid,item`` CSV files; every
             worker's transactions are its own (tids disjoint between workers' files)
             (daal_ar/Aprior/ARDaalCollectiveMapper.java)  [--min-support 0.001
@@ -84,7 +89,7 @@ EXTRA = {  # named-only flags
     "ccd": [("num_users", int, 0), ("num_items", int, 0)],
     "daal": [("k", int, 0), ("method", str, ""), ("label_cols", int, 1), ("n_trees", int, 50), ("max_depth", int, 10),
              ("engine", str, "native"), ("format", str, "dense"), ("labels", str, ""),
-             ("min_support", float, 0.001), ("min_confidence", float, 0.7)],
+             ("min_support", float, 0.001), ("min_confidence", float, 0.7), ("rounds", int, 50), ("c", float, 2.0)],
     "mds": [("work_dir", str, "harp-work/mds"), ("checkpoint_every", int, 0)],
 }
 
@@ -466,9 +471,56 @@ def _run_daal(comm, cfg):
                                      torch.cat([t.threshold for t in forest.trees]),
                                      torch.cat([t.left for t in forest.trees]).double()], 1),
                "values": torch.cat([t.value for t in forest.trees]), "n_trees": len(forest.trees)}
+    elif algo in ("adaboost", "logitboost", "brownboost", "stump"):
+        out = _run_daal_boost(comm, cfg, A)
     else:
         raise ValueError(f"unknown daal algo {algo}")
     return _save_daal(comm, cfg, out)
+
+
+def _run_daal_boost(comm, cfg, A):
+    """Boosted stumps on the workers' row shards (daal_adaboost, daal_logitboost,
+    daal_brownboost, daal_stump). Rank 0 writes the learners as ``dforest`` writes its trees
+    (nodes = (learner, feature, threshold, left), values [N, C]) plus ``alphas``. LogitBoost's
+    learner t * K + k is the stump of class k in round t."""
+    from .models import trees as TR
+
+    algo, engine = cfg["algo"], cfg["engine"]
+    if algo in ("brownboost", "stump") and comm.world_size != 1:
+        raise ValueError(f"daal {algo} trains on one worker's rows: run it with maps = 1")
+    A = A.to(comm.device)
+    X, yr = A[:, :-1], A[:, -1]
+    signed = _allmax(comm, int(bool((yr < 0).any())))  # the reference's -1 / +1 fixtures
+    y = (yr > 0).long() if signed else yr.long()
+    k = cfg["k"] or _allmax(comm, int(y.max()) + 1 if y.numel() else 0)
+    if algo in ("brownboost", "stump"):
+        if algo == "stump":
+            learners, alphas = [TR.stump(X, y, num_classes=k, engine=engine)], [1.0]
+        else:
+            m = TR.BrownBoost(c=cfg["c"], max_rounds=cfg["rounds"], engine=engine).fit(X, y)
+            learners, alphas = m.learners, m.alphas
+    else:
+        m = (TR.AdaBoost(cfg["rounds"], engine=engine) if algo == "adaboost"
+             else TR.LogitBoost(cfg["rounds"], engine=engine))
+        if engine == "native":
+            m.fit_distributed(X, y, comm, num_classes=k)
+        else:  # the torch engine has no sharded fit: every worker trains on all rows
+            from .parallel.partition_util import allgather_objects
+
+            Xa = torch.cat(allgather_objects(comm, [torch.cat([X, y.double()[:, None]], 1).cpu()])).to(comm.device)
+            m.fit(Xa[:, :-1], Xa[:, -1].long(), num_classes=k)
+        if algo == "adaboost":
+            learners, alphas = m.learners, m.alphas
+        else:
+            learners = [f for fs in m.rounds for f in fs]
+            alphas = [1.0] * len(learners)
+    tid = torch.cat([torch.full((t.feature.numel(),), float(i), dtype=torch.float64)
+                     for i, t in enumerate(learners)])
+    return {"nodes": torch.stack([tid, torch.cat([t.feature for t in learners]).double(),
+                                  torch.cat([t.threshold for t in learners]),
+                                  torch.cat([t.left for t in learners]).double()], 1),
+            "values": torch.cat([t.value for t in learners]), "alphas": torch.tensor(alphas, dtype=torch.float64),
+            "n_learners": len(learners)}
 
 
 def _run_daal_ar(comm, cfg, files):

@@ -23,7 +23,18 @@ children numbered in level order, left then right):
   wave per (node, feature) split search and a packed-forest prediction kernel. HIP tensors
   run the kernels, CPU tensors the torch mirror of the same algorithm. ``DecisionForest`` can
   then also train one model over row shards (``fit_distributed(mode="rows")``: one histogram
-  all-reduce per level). The boosting classes use the torch engine.
+  all-reduce per level).
+
+The boosting classes (``stump``, ``AdaBoost``, ``LogitBoost``, ``BrownBoost``) take the same
+``engine`` argument. ``"torch"`` (default) fits a fresh ``DecisionTree`` per learner.
+``"native"`` — ``ops/boost.py`` + ``csrc/boost.hip`` — bins the features once per fit and runs
+one fused pass over the binned rows per round (the previous learner's weight or
+working-response update plus the root histogram), then the forest engine's split kernels;
+BrownBoost's search for the time step runs on the device. The learners are ordinary
+``DecisionTree`` objects, so models of the two engines are interchangeable, and
+``AdaBoost`` / ``LogitBoost`` can train one model over row shards (``fit_distributed``: one
+histogram all-reduce per round). On HIP tensors their ``decision`` walks all stumps in the
+packed-forest prediction kernel.
 """
 from __future__ import annotations
 
@@ -34,6 +45,7 @@ from typing import List, Optional
 import torch
 
 from ..core.writable import DataInput, DataOutput, Writable
+from ..ops import boost as BO
 from ..ops import forest as F
 from ..parallel.comm import Communicator
 
@@ -421,20 +433,104 @@ class DecisionForest:
 
 
 # ---------------------------------------------------------------- boosting
-def stump(X, y, sample_weight=None, num_classes=None, task="classification"):
-    """Decision stump (daal_stump): a depth-1 tree."""
-    return DecisionTree(task, max_depth=1, n_bins=256).fit(X, y, sample_weight, num_classes)
+def _check_engine(engine: str) -> str:
+    if engine not in ENGINES:
+        raise ValueError(f"engine must be one of {ENGINES} (got {engine!r})")
+    return engine
+
+
+def _stump_tree(task: str, n_bins: int, split: bool, feature: int, threshold: float, values) -> DecisionTree:
+    """A depth-1 ``DecisionTree`` from (root, left, right) node values [3, C]; a bare root if
+    ``split`` is false."""
+    t = DecisionTree(task, max_depth=1, n_bins=n_bins, engine="native")
+    m = 3 if split else 1
+    t.feature = torch.tensor([feature if split else -1, -1, -1][:m], dtype=torch.int64)
+    t.threshold = torch.tensor([threshold if split else 0.0, 0.0, 0.0][:m], dtype=torch.float64)
+    t.left = torch.tensor([1 if split else -1, -1, -1][:m], dtype=torch.int64)
+    t.value = torch.as_tensor(values, dtype=torch.float64)[:m].reshape(m, -1)
+    return t
+
+
+def _class_stump(info, th: torch.Tensor, C: int) -> DecisionTree:
+    """Classification stump from a ``ops.boost.class_finish`` record (``th`` on the CPU)."""
+    f, b = int(info[1]), int(info[2])
+    L = torch.tensor(info[BO.INFO:BO.INFO + C], dtype=torch.float64)
+    R = torch.tensor(info[BO.INFO + C:BO.INFO + 2 * C], dtype=torch.float64)
+    V = torch.stack([L + R, L, R])
+    V = V / V.sum(1, keepdim=True).clamp_min(1e-300)
+    return _stump_tree("classification", th.shape[1] + 1, bool(info[0]), f, float(th[f, b]), V)
+
+
+def _shards(X, y, comm: Communicator, num_classes, thresholds, n_bins: int):
+    """What the workers of a row-sharded fit agree on first: (classes, thresholds, total rows).
+    Rank 0's quantiles serve everyone, as in ``DecisionForest._fit_rows``."""
+    n_total = int(comm.all_gather_ints([X.shape[0]])[:, 0].sum())
+    if num_classes is None:
+        top = torch.tensor([int(y.max()) if y.numel() else 0], dtype=torch.int64, device=comm.device)
+        comm.all_reduce(top, op=torch.distributed.ReduceOp.MAX)
+        num_classes = int(top) + 1
+    th = thresholds
+    if th is None:
+        th = _bins(X, n_bins) if comm.rank == 0 else torch.empty((X.shape[1], n_bins - 1), dtype=torch.float64,
+                                                                 device=X.device)
+        th = th.contiguous()
+        comm.broadcast(th, 0)
+    return int(num_classes), th.to(X.device), n_total
+
+
+def _packed_sum(X, trees, values, K: int, cache: dict):
+    """Sum over ``trees`` of their leaf rows in ``values`` (one [nodes, K] tensor per tree)
+    through the packed-forest prediction kernel, [n, K] fp64. ``cache`` keeps the pack while
+    the device and the tree arrays stay the same objects and ``values`` compare equal."""
+    arrays = [a for t in trees for a in (t.feature, t.threshold, t.left, t.value)]
+    hit = (cache.get("device") == str(X.device) and len(cache["arrays"]) == len(arrays)
+           and all(a is b for a, b in zip(cache["arrays"], arrays))
+           and all(torch.equal(a, b) for a, b in zip(cache["values"], values)))
+    if not hit:
+        from types import SimpleNamespace
+
+        cache["device"], cache["arrays"], cache["values"] = str(X.device), arrays, values
+        cache["pack"] = F.pack_trees([SimpleNamespace(feature=t.feature, threshold=t.threshold, left=t.left, value=v)
+                                      for t, v in zip(trees, values)], X.device)
+    return F.predict_packed(X, cache["pack"])[0] * len(trees)
+
+
+def stump(X, y, sample_weight=None, num_classes=None, task="classification", engine="torch"):
+    """Decision stump (daal_stump): a depth-1 tree. ``engine="native"`` (classification): one
+    round of ``ops.boost`` with the weights scaled to sum n."""
+    if _check_engine(engine) == "torch":
+        return DecisionTree(task, max_depth=1, n_bins=256).fit(X, y, sample_weight, num_classes)
+    if task != "classification":
+        return DecisionTree(task, max_depth=1, n_bins=256, engine="native").fit(X, y, sample_weight, num_classes)
+    n, d = X.shape
+    C = int(num_classes or int(y.max()) + 1)
+    F.check_shape(256, C)
+    th = _bins(X, 256)
+    w0 = None if sample_weight is None else sample_weight.double().to(X.device) * (n / float(sample_weight.sum()))
+    got = []
+    BO.ada_fit(F.bin_features(X, th), y.to(X.device), d, 256, C, 1, w0=w0, trace=lambda t, s: got.append(s["info"]))
+    return _class_stump(got[0], th.cpu(), C)
 
 
 class AdaBoost:
     """Multi-class AdaBoost (SAMME) with stumps (daal_adaboost)."""
 
-    def __init__(self, n_rounds=50, learner_depth=1):
+    def __init__(self, n_rounds=50, learner_depth=1, engine="torch"):
+        self.engine = _check_engine(engine)
         self.n_rounds, self.depth = n_rounds, learner_depth
         self.learners, self.alphas = [], []
+        self.errors: List[float] = []  # native engine: the weighted error of every learner kept
+        self._pack: dict = {}
 
-    def fit(self, X, y, num_classes=None):
+    def fit(self, X, y, num_classes=None, thresholds=None, trace=None):
+        """``thresholds`` / ``trace`` (per round: ``H``, feature, bin, err, alpha) are the
+        native engine's; the torch engine raises when given either."""
         K = num_classes or int(y.max()) + 1
+        if self.engine == "native":
+            return self._fit_native(X, y, int(K), thresholds if thresholds is not None else _bins(X, 256),
+                                    trace=trace)
+        if thresholds is not None or trace is not None:
+            raise ValueError('thresholds / trace need engine="native"')
         n = X.shape[0]
         w = torch.full((n,), 1.0 / n, dtype=torch.float64, device=X.device)
         yl = y.long().to(X.device)
@@ -454,7 +550,70 @@ class AdaBoost:
                 break
         return self
 
+    def _fit_native(self, X, y, K: int, th, reduce=None, n_total=None, trace=None):
+        """Bin once, then one fused round per stump (``ops.boost.ada_fit``). Deeper learners
+        are grown by ``ops.forest.grow`` on the shared bins with the update in torch."""
+        n, d = X.shape
+        dev = X.device
+        B = th.shape[1] + 1
+        F.check_shape(B, K)
+        self.K = K
+        self._pack = {}
+        Xb = F.bin_features(X, th)
+        if self.depth == 1:
+            thc = th.cpu()
+            for info in BO.ada_fit(Xb, y.to(dev), d, B, K, self.n_rounds, n_total=n_total, reduce=reduce, trace=trace):
+                self.learners.append(_class_stump(info, thc, K))
+                self.alphas.append(info[6])
+                self.errors.append(info[5])
+            return self
+        if reduce is not None:
+            raise ValueError("fit_distributed supports learner_depth=1 only")
+        yl = y.long().to(dev)
+        Y = torch.nn.functional.one_hot(yl, K).double()
+        w = torch.ones(n, dtype=torch.float64, device=dev)
+        one = torch.ones((1, n), dtype=torch.uint8, device=dev)
+        proto = DecisionTree("classification", self.depth, n_bins=B, engine="native")
+        for _ in range(self.n_rounds):
+            packed = F.grow(Xb, d, B, K, F.REAL, one, task=F.GINI, max_depth=self.depth, min_leaf=1.0,
+                            stats=Y * w[:, None])
+            h = _trees_from_packed(packed, th, proto, [0])[0]
+            miss = (F.predict_packed(X, F.pack_trees([h], dev))[0].argmax(1) != yl).double()
+            err = float((w * miss).sum() / w.sum())
+            if err >= 1 - 1.0 / K:
+                break
+            a = math.log((1 - err) / max(err, 1e-12)) + math.log(K - 1)
+            self.learners.append(h)
+            self.alphas.append(a)
+            self.errors.append(err)
+            w = w * torch.exp(a * miss)
+            w = w * (n / w.sum())
+            if err < 1e-12:
+                break
+        return self
+
+    def fit_distributed(self, X, y, comm: Communicator, num_classes=None, thresholds=None):
+        """One model over the workers' row shards (native engine, stumps): rank 0's quantiles,
+        one histogram all-reduce per round; every worker ends with the same learners."""
+        if self.engine != "native":
+            raise ValueError('fit_distributed needs engine="native"')
+        K, th, n_total = _shards(X, y, comm, num_classes, thresholds, 256)
+        return self._fit_native(X, y, K, th, reduce=lambda H: comm.all_reduce(H), n_total=n_total)
+
+    def _decision_packed(self, X):
+        """All learners in one pass of the packed-forest kernel: leaf values alpha * e_class."""
+        if not self.learners:
+            return torch.zeros((X.shape[0], self.K), dtype=torch.float64, device=X.device)
+        vals = [a * torch.nn.functional.one_hot(h.value.argmax(1), self.K).double()
+                for h, a in zip(self.learners, self.alphas)]
+        return _packed_sum(X, self.learners, vals, self.K, self._pack)
+
     def decision(self, X):
+        if self.engine == "native" and X.device.type == "cuda":
+            return self._decision_packed(X)
+        return self._decision_loop(X)
+
+    def _decision_loop(self, X):
         S = torch.zeros((X.shape[0], self.K), dtype=torch.float64, device=X.device)
         for h, a in zip(self.learners, self.alphas):
             S[torch.arange(X.shape[0], device=X.device), h.predict(X)] += a
@@ -462,6 +621,56 @@ class AdaBoost:
 
     def predict(self, X):
         return self.decision(X).argmax(1)
+
+
+def brown_line_search(r, u, s: float, c: float, iters: int, nu: float):
+    """The BrownBoost step (alpha, t) for margins ``r``, learner agreement ``u`` (+-1),
+    remaining time ``s`` and budget ``c``: t(alpha) keeps the total potential constant, alpha
+    zeroes the weighted correlation after the step (nested bisections, every probe read on
+    the host)."""
+
+    def pot(z):
+        return (1 - torch.erf(z / math.sqrt(c))).sum()
+
+    target = pot(r + s)
+
+    def t_of(a):
+        lo, hi = 0.0, s
+        if float(pot(r + s - hi + a * u)) <= float(target):
+            return hi
+        for _ in range(iters):
+            mid = 0.5 * (lo + hi)
+            if float(pot(r + s - mid + a * u)) < float(target):
+                lo = mid
+            else:
+                hi = mid
+        return 0.5 * (lo + hi)
+
+    def corr(a):
+        t = t_of(a)
+        z = r + s - t + a * u
+        return float((torch.exp(-z * z / c) * u).sum()), t
+
+    a_lo, a_hi = 0.0, 1.0
+    g_hi, t_hi = corr(a_hi)
+    while g_hi > 0 and t_hi < s and a_hi < 1e3:
+        a_lo, a_hi = a_hi, a_hi * 2
+        g_hi, t_hi = corr(a_hi)
+    if g_hi > 0:  # time runs out before the correlation vanishes
+        a, t = a_hi, t_hi
+    else:
+        for _ in range(iters):
+            mid = 0.5 * (a_lo + a_hi)
+            g, _t = corr(mid)
+            if g > 0:
+                a_lo = mid
+            else:
+                a_hi = mid
+            if a_hi - a_lo < nu * 1e-3:
+                break
+        a = 0.5 * (a_lo + a_hi)
+        t = t_of(a)
+    return a, t
 
 
 class BrownBoost:
@@ -472,14 +681,52 @@ class BrownBoost:
     correlation of the learner after the step (both by bisection: robust also when the
     weak learner is nearly perfect). Stops when the remaining time s reaches 0."""
 
-    def __init__(self, c: float = 2.0, max_rounds: int = 100, nu: float = 1e-3, newton_iters: int = 60):
+    def __init__(self, c: float = 2.0, max_rounds: int = 100, nu: float = 1e-3, newton_iters: int = 60,
+                 engine: str = "torch"):
+        self.engine = _check_engine(engine)
         self.c, self.max_rounds, self.nu, self.iters = c, max_rounds, nu, newton_iters
         self.learners, self.alphas = [], []
+        self.host_reads: List[int] = []  # native engine: device -> host reads of every round
 
-    def _pot(self, z):
-        return (1 - torch.erf(z / math.sqrt(self.c))).sum()
+    def _fit_native(self, X, y, th):
+        """Bin once; per round one fused pass (weights exp(-(r + s)^2 / c) from ``r`` and the
+        root histogram, scaled to sum n), the split kernels, and ``ops.boost.brown_solve``."""
+        n, d = X.shape
+        dev = X.device
+        B = th.shape[1] + 1
+        F.check_shape(B, 2)
+        Xb = F.bin_features(X, th)
+        thc = th.cpu()
+        yi = y.to(dev).int().contiguous()
+        ys = (2 * yi - 1).double()
+        r = torch.zeros(n, dtype=torch.float64, device=dev)
+        rec, mul = BO.new_class_state(dev)
+        s = self.c
+        for _ in range(self.max_rounds):
+            if s <= 1e-9:
+                break
+            scal = torch.tensor([s, self.c], dtype=torch.float64, device=dev)
+            H = BO.class_round(Xb, yi, None, None, None, None, d, B, 2, r=r, scal=scal)
+            H = H * (n / H[0, 0].sum())
+            bf, bb, _, sp, L, R, T = BO.root_split(H, F.GINI)
+            info = BO.class_finish(bf, bb, sp, L, R, T, float(n), rec, mul).tolist()
+            if not info[0] or info[5] >= 0.5:  # sum(w u) = S (1 - 2 err) <= 0
+                break
+            pred = torch.where(Xb[:, int(info[1])] > int(info[2]), int(info[4]), int(info[3]))
+            u = (2 * pred - 1).double() * ys
+            a, t, reads = BO.brown_solve(r, u, s, self.c, self.iters, self.nu)
+            r = r + a * u
+            s -= max(t, self.nu)
+            self.learners.append(_class_stump(info, thc, 2))
+            self.alphas.append(a)
+            self.host_reads.append(reads + 1)
+        return self
 
-    def fit(self, X, y):
+    def fit(self, X, y, thresholds=None):
+        if self.engine == "native":
+            return self._fit_native(X, y, thresholds if thresholds is not None else _bins(X, 256))
+        if thresholds is not None:
+            raise ValueError('thresholds need engine="native"')
         yl = y.long().to(X.device)
         ys = (2 * yl - 1).double()  # {-1, +1}
         r = torch.zeros(X.shape[0], dtype=torch.float64, device=X.device)
@@ -492,44 +739,7 @@ class BrownBoost:
             u = (2 * h.predict(X) - 1).double() * ys
             if float((w * u).sum()) <= 0:
                 break
-            target = self._pot(r + s)
-
-            def t_of(a):
-                lo, hi = 0.0, s
-                if float(self._pot(r + s - hi + a * u)) <= float(target):
-                    return hi
-                for _ in range(self.iters):
-                    mid = 0.5 * (lo + hi)
-                    if float(self._pot(r + s - mid + a * u)) < float(target):
-                        lo = mid
-                    else:
-                        hi = mid
-                return 0.5 * (lo + hi)
-
-            def corr(a):
-                t = t_of(a)
-                z = r + s - t + a * u
-                return float((torch.exp(-z * z / self.c) * u).sum()), t
-
-            a_lo, a_hi = 0.0, 1.0
-            g_hi, t_hi = corr(a_hi)
-            while g_hi > 0 and t_hi < s and a_hi < 1e3:
-                a_lo, a_hi = a_hi, a_hi * 2
-                g_hi, t_hi = corr(a_hi)
-            if g_hi > 0:  # time runs out before the correlation vanishes
-                a, t = a_hi, t_hi
-            else:
-                for _ in range(self.iters):
-                    mid = 0.5 * (a_lo + a_hi)
-                    g, _t = corr(mid)
-                    if g > 0:
-                        a_lo = mid
-                    else:
-                        a_hi = mid
-                    if a_hi - a_lo < self.nu * 1e-3:
-                        break
-                a = 0.5 * (a_lo + a_hi)
-                t = t_of(a)
+            a, t = brown_line_search(r, u, s, self.c, self.iters, self.nu)
             r = r + a * u
             s -= max(t, self.nu)
             self.learners.append(h)
@@ -550,12 +760,84 @@ class LogitBoost:
     """Multi-class LogitBoost (Friedman, Hastie & Tibshirani 2000; daal_logitboost) with
     regression stumps fit to the Newton working responses."""
 
-    def __init__(self, n_rounds=50, depth=1, zmax=4.0):
+    def __init__(self, n_rounds=50, depth=1, zmax=4.0, engine="torch"):
+        self.engine = _check_engine(engine)
         self.n_rounds, self.depth, self.zmax = n_rounds, depth, zmax
         self.rounds: List[List[DecisionTree]] = []
+        self._pack: dict = {}
 
-    def fit(self, X, y, num_classes=None):
+    def _fit_native(self, X, y, K: int, th, reduce=None, trace=None):
+        """Bin once, then one fused round for all K stumps (``ops.boost.logit_fit``: no host
+        read until the end). Deeper learners are grown by ``ops.forest.grow`` on the shared
+        bins with the update in torch."""
+        n, d = X.shape
+        dev = X.device
+        B = th.shape[1] + 1
+        F.check_shape(B, K)
+        self.K = K
+        self._pack = {}
+        Xb = F.bin_features(X, th)
+        if self.depth == 1:
+            thc = th.cpu()
+            ri, rv, root = BO.logit_fit(Xb, y.to(dev), d, B, K, self.n_rounds, self.zmax, reduce=reduce, trace=trace)
+            for t in range(ri.shape[0]):
+                fs = []
+                for k in range(K):
+                    f, b = int(ri[t, k, 0]), int(ri[t, k, 1])
+                    fs.append(_stump_tree("regression", B, f >= 0, f, float(thc[f, b]) if f >= 0 else 0.0,
+                                          [float(root[t, k]), float(rv[t, k, 0]), float(rv[t, k, 1])]))
+                self.rounds.append(fs)
+            return self
+        if reduce is not None:
+            raise ValueError("fit_distributed supports depth=1 only")
+        Y = torch.nn.functional.one_hot(y.long().to(dev), K).double()
+        Fm = torch.zeros((n, K), dtype=torch.float64, device=dev)
+        one = torch.ones((1, n), dtype=torch.uint8, device=dev)
+        proto = DecisionTree("regression", self.depth, n_bins=B, engine="native")
+        for _ in range(self.n_rounds):
+            Pm = torch.softmax(Fm, 1)
+            fs = []
+            for k in range(K):
+                p = Pm[:, k]
+                w = (p * (1 - p)).clamp_min(1e-12)
+                z = ((Y[:, k] - p) / w).clamp(-self.zmax, self.zmax)
+                packed = F.grow(Xb, d, B, 3, F.REAL, one, task=F.MSE, max_depth=self.depth, min_leaf=1.0,
+                                stats=torch.stack([w, w * z, w * z * z], 1))
+                fs.append(_trees_from_packed(packed, th, proto, [0])[0])
+            G = torch.cat([F.predict_packed(X, F.pack_trees([f], dev))[0] for f in fs], 1)
+            Fm = Fm + (K - 1) / K * (G - G.mean(1, keepdim=True))
+            self.rounds.append(fs)
+        return self
+
+    def fit_distributed(self, X, y, comm: Communicator, num_classes=None, thresholds=None):
+        """One model over the workers' row shards (native engine, stumps): rank 0's quantiles,
+        one histogram all-reduce per round; every worker ends with the same learners."""
+        if self.engine != "native":
+            raise ValueError('fit_distributed needs engine="native"')
+        K, th, _ = _shards(X, y, comm, num_classes, thresholds, 256)
+        return self._fit_native(X, y, K, th, reduce=lambda H: comm.all_reduce(H))
+
+    def _decision_packed(self, X):
+        """All rounds * K learners in one pass of the packed-forest kernel (learner (t, k)
+        carries its value in column k), centred once."""
+        K = self.K
+        trees = [f for fs in self.rounds for f in fs]
+        if not trees:
+            return torch.zeros((X.shape[0], K), dtype=torch.float64, device=X.device)
+        vals = [f.value * torch.nn.functional.one_hot(torch.tensor(i % K), K).double()[None, :]
+                for i, f in enumerate(trees)]
+        S = _packed_sum(X, trees, vals, K, self._pack)
+        return (K - 1) / K * (S - S.mean(1, keepdim=True))
+
+    def fit(self, X, y, num_classes=None, thresholds=None, trace=None):
+        """``thresholds`` / ``trace`` (per round: ``H`` and the K splits) are the native engine's;
+        the torch engine raises when given either."""
         K = num_classes or int(y.max()) + 1
+        if self.engine == "native":
+            return self._fit_native(X, y, int(K), thresholds if thresholds is not None else _bins(X, 256),
+                                    trace=trace)
+        if thresholds is not None or trace is not None:
+            raise ValueError('thresholds / trace need engine="native"')
         self.K = K
         n = X.shape[0]
         Y = torch.nn.functional.one_hot(y.long().to(X.device), K).double()
@@ -576,6 +858,11 @@ class LogitBoost:
         return self
 
     def decision(self, X):
+        if self.engine == "native" and X.device.type == "cuda":
+            return self._decision_packed(X)
+        return self._decision_loop(X)
+
+    def _decision_loop(self, X):
         F = torch.zeros((X.shape[0], self.K), dtype=torch.float64, device=X.device)
         for fs in self.rounds:
             G = torch.stack([f.predict(X) for f in fs], 1)
