@@ -32,6 +32,14 @@ same parameters as named flags (which win when both are given):
             worker's transactions are its own (tids disjoint between workers' files)
             (daal_ar/Aprior/ARDaalCollectiveMapper.java)  [--min-support 0.001
             --min-confidence 0.7 --engine native|torch --k items]
+            algo svm: one-against-one SVM (daal_svm/MultiClassDenseBatch, MultiClassCSRBatch),
+            maps = 1. Dense rows: last column = label; ``--format csr``: DAAL CSR text with
+            ``--labels``, never densified. Writes svm_sv_index.csv, svm_coef.csv (machine a,
+            machine b, training row, coefficient), svm_bias.csv and, with a test set,
+            svm_predictions.csv  [--kernel linear|rbf --sigma 1.0 --c 1.0 --k classes
+            --test-dir --test-labels (csr)]
+            algo kernel: the kernel function of the input against itself (daal_kernel_func
+            matrixMatrix mode) -> kernel_values.csv  [--kernel linear|rbf --sigma --format]
 
 ``maps`` = number of workers. Outside torchrun the CLI spawns ``maps`` local worker
 processes (RCCL on GPUs when ``maps`` <= visible GPUs, else gloo on CPU); under torchrun
@@ -89,7 +97,8 @@ EXTRA = {  # named-only flags
     "ccd": [("num_users", int, 0), ("num_items", int, 0)],
     "daal": [("k", int, 0), ("method", str, ""), ("label_cols", int, 1), ("n_trees", int, 50), ("max_depth", int, 10),
              ("engine", str, "native"), ("format", str, "dense"), ("labels", str, ""),
-             ("min_support", float, 0.001), ("min_confidence", float, 0.7), ("rounds", int, 50), ("c", float, 2.0)],
+             ("min_support", float, 0.001), ("min_confidence", float, 0.7), ("rounds", int, 50), ("c", float, None),
+             ("kernel", str, "linear"), ("sigma", float, 1.0), ("test_dir", str, ""), ("test_labels", str, "")],
     "mds": [("work_dir", str, "harp-work/mds"), ("checkpoint_every", int, 0)],
 }
 
@@ -427,6 +436,8 @@ def _run_daal(comm, cfg):
     out: Dict[str, Any] = {}
     if algo in ("ar", "apriori"):
         return _save_daal(comm, cfg, _run_daal_ar(comm, cfg, files))
+    if algo in ("svm", "kernel"):
+        return _save_daal(comm, cfg, _run_daal_svm(comm, cfg, files))
     if cfg["format"] == "csr":
         return _save_daal(comm, cfg, _run_daal_csr(comm, cfg, files))
     if cfg["format"] != "dense":
@@ -497,7 +508,7 @@ def _run_daal_boost(comm, cfg, A):
         if algo == "stump":
             learners, alphas = [TR.stump(X, y, num_classes=k, engine=engine)], [1.0]
         else:
-            m = TR.BrownBoost(c=cfg["c"], max_rounds=cfg["rounds"], engine=engine).fit(X, y)
+            m = TR.BrownBoost(c=2.0 if cfg["c"] is None else cfg["c"], max_rounds=cfg["rounds"], engine=engine).fit(X, y)
             learners, alphas = m.learners, m.alphas
     else:
         m = (TR.AdaBoost(cfg["rounds"], engine=engine) if algo == "adaboost"
@@ -542,6 +553,93 @@ def _run_daal_ar(comm, cfg, files):
     return out
 
 
+def _run_daal_svm(comm, cfg, files):
+    """``algo=svm``: one-against-one SVM on one worker's rows (daal_svm/MultiClassDenseBatch,
+    MultiClassCSRBatch: linear kernel, 5 classes unless ``--k``), and ``algo=kernel``: the
+    kernel function of the input against itself (daal_kernel_func, matrixMatrix mode). CSR
+    input is never densified. ``svm_coef`` has one row per (machine, support vector):
+    machine classes a and b, the training row and its coefficient alpha_i y_i."""
+    from .models import svm as SV
+    from .utils.datasets import load_dense_csv
+
+    algo, fmt, kernel, sigma = cfg["algo"], cfg["format"], cfg["kernel"], cfg["sigma"]
+    if comm.world_size != 1:
+        raise ValueError(f"daal {algo} runs on one worker's rows: run it with maps = 1")
+    if fmt not in ("dense", "csr"):
+        raise ValueError(f"format={fmt!r}: expected 'dense' or 'csr'")
+    if kernel not in ("linear", "rbf"):
+        raise ValueError(f"kernel={kernel!r}: expected 'linear' or 'rbf'")
+    dev = comm.device
+
+    def labels_of(path, fs):
+        pair = dict(zip(sorted(_files(path[0])), sorted(_files(path[1]))))
+        return torch.cat([load_dense_csv(pair[f]).reshape(-1) for f in fs]).long()
+
+    def load(path, lab, width=0):
+        fs = _files(path)
+        if fmt == "csr":
+            X = _load_csr_files(fs, width=width)
+            y = labels_of((path, lab), fs) if lab else None
+            return X.to(dev), y
+        A = torch.cat([load_dense_csv(f) for f in fs]).double()
+        if algo == "kernel":
+            return A.to(dev), None
+        return A[:, :-1].to(dev), A[:, -1].long()
+
+    if algo == "kernel":
+        X, _ = load(cfg["input_dir"], "")
+        return {"values": SV.kernel_matrix(X, X, kernel, sigma)}
+    if fmt == "csr" and not cfg["labels"]:
+        raise ValueError("algo=svm with format=csr needs --labels")
+    test = load(cfg["test_dir"], cfg["test_labels"]) if cfg["test_dir"] else None
+    X, y = load(cfg["input_dir"], cfg["labels"], width=test[0].shape[1] if test and fmt == "csr" else 0)
+    k = cfg["k"] or int(y.max()) + 1
+    model = SV.MultiClassSVM(k, C=1.0 if cfg["c"] is None else cfg["c"], kernel=kernel, sigma=sigma).fit(X, y.to(dev))
+    rows, sv = [], set()
+    for (a, b), m in model.machines.items():
+        idx = torch.nonzero((y == a) | (y == b)).reshape(-1)[m.sv_index.cpu()]  # training rows of the SVs
+        sv.update(idx.tolist())
+        rows.append(torch.stack([torch.full_like(idx, a).double(), torch.full_like(idx, b).double(), idx.double(),
+                                 m.coef.cpu()], 1))
+    out = {"sv_index": torch.tensor(sorted(sv), dtype=torch.float64),
+           "coef": torch.cat(rows) if rows else torch.zeros((0, 4), dtype=torch.float64),
+           "bias": torch.tensor([[a, b, m.bias] for (a, b), m in model.machines.items()],
+                                dtype=torch.float64).reshape(-1, 3),
+           "n_sv": len(sv), "train_error": float((model.predict(X).cpu() != y).double().mean()), "test_error": None}
+    if cfg["test_dir"]:
+        Xt, yt = test
+        if fmt == "csr" and Xt.shape[1] < X.shape[1]:  # a CSR file ends at its own largest column
+            Xt = torch.sparse_csr_tensor(Xt.crow_indices(), Xt.col_indices(), Xt.values(),
+                                         size=(Xt.shape[0], X.shape[1]))
+        if Xt.shape[1] != X.shape[1]:
+            raise ValueError(f"test rows have {Xt.shape[1]} columns, training rows {X.shape[1]}")
+        pred = model.predict(Xt).cpu()
+        out["predictions"] = pred.double()
+        if yt is not None:
+            out["test_error"] = float((pred != yt).double().mean())
+    return out
+
+
+def _load_csr_files(files, agree=None, width: int = 0):
+    """The DAAL CSR text files as one CSR tensor (rows concatenated). The files differ in
+    width (each ends at its own largest column): ``agree`` maps the local width to the common
+    one, ``width`` is a lower bound (a test set is as wide as its training set)."""
+    from .utils.datasets import load_daal_csr
+
+    blocks = [load_daal_csr(f) for f in files]
+    d = max(max((b.shape[1] for b in blocks), default=0), width)
+    if agree is not None:
+        d = agree(d)
+    rp, off = [torch.zeros(1, dtype=torch.long)], 0
+    for b in blocks:
+        rp.append(b.crow_indices()[1:] + off)
+        off += b.values().numel()
+    cat = (lambda xs, dt: torch.cat(xs) if xs else torch.zeros(0, dtype=dt))
+    rowptr = torch.cat(rp)
+    return torch.sparse_csr_tensor(rowptr, cat([b.col_indices() for b in blocks], torch.long),
+                                   cat([b.values() for b in blocks], torch.float64), size=(rowptr.numel() - 1, d))
+
+
 def _run_daal_csr(comm, cfg, files):
     """``format=csr``: DAAL CSR text files (three lines: row offsets, columns, values), never
     densified. The files of the reference's fixtures differ in width (each ends at its own
@@ -550,19 +648,10 @@ def _run_daal_csr(comm, cfg, files):
     in sorted order."""
     from .models import naive_bayes as NB
     from .models import stats as ST
-    from .utils.datasets import load_daal_csr, load_dense_csv
+    from .utils.datasets import load_dense_csv
 
     algo = cfg["algo"]
-    blocks = [load_daal_csr(f) for f in files]
-    d = _allmax(comm, max((b.shape[1] for b in blocks), default=0))
-    rp, off = [torch.zeros(1, dtype=torch.long)], 0
-    for b in blocks:
-        rp.append(b.crow_indices()[1:] + off)
-        off += b.values().numel()
-    cat = (lambda xs, dt: torch.cat(xs) if xs else torch.zeros(0, dtype=dt))
-    rowptr = torch.cat(rp)
-    A = torch.sparse_csr_tensor(rowptr, cat([b.col_indices() for b in blocks], torch.long),
-                                cat([b.values() for b in blocks], torch.float64), size=(rowptr.numel() - 1, d))
+    A = _load_csr_files(files, lambda w: _allmax(comm, w))
     if algo in ("cov", "covariance"):
         return ST.covariance(A, comm)
     if algo in ("mom", "moments"):

@@ -36,8 +36,23 @@ def _dense(X):
     return X.to_dense() if (X.is_sparse or X.layout in (torch.sparse_csr, torch.sparse_csc)) else X
 
 
+def _sp(X) -> bool:
+    return X.is_sparse or X.layout == torch.sparse_csr
+
+
+def _sparse_block(X, Y, kind, **kw):
+    """Both operands sparse: the dense block from the CSR arrays (``ops.csr_kernel``: HIP on
+    the GPU, the torch reference on the CPU), neither operand densified."""
+    from ..ops import csr_kernel as CK
+
+    K = CK.kernel_block(X, Y, kind, **kw)
+    return K if X.dtype == torch.float64 or not X.dtype.is_floating_point else K.to(X.dtype)
+
+
 def _mm_t(X, Y):
     """X @ Y^T for dense or sparse X / Y."""
+    if _sp(X) and _sp(Y):
+        return _sparse_block(X, Y, "gram")
     if X.is_sparse or X.layout == torch.sparse_csr:
         return torch.sparse.mm(X, _dense(Y).t().contiguous())
     if Y.is_sparse or Y.layout == torch.sparse_csr:
@@ -56,11 +71,15 @@ def _sqnorm(X):
 
 def linear_kernel(X, Y, k: float = 1.0, b: float = 0.0) -> torch.Tensor:
     """K[i, j] = k <x_i, y_j> + b (dense or CSR inputs)."""
+    if _sp(X) and _sp(Y):
+        return _sparse_block(X, Y, "linear", k=k, b=b)
     return k * _mm_t(X, Y) + b
 
 
 def sq_distances(X, Y) -> torch.Tensor:
     """||x_i - y_j||^2 via ||x||^2 + ||y||^2 - 2 X Y^T (one GEMM, clamped at 0)."""
+    if _sp(X) and _sp(Y):
+        return _sparse_block(X, Y, "sqdist")
     G = _mm_t(X, Y)
     return (_sqnorm(X)[:, None] + _sqnorm(Y)[None, :] - 2 * G).clamp_min(0)
 
@@ -75,7 +94,10 @@ _lib.register({
 def rbf_kernel(X, Y, sigma: float = 1.0) -> torch.Tensor:
     """K[i, j] = exp(-||x_i - y_j||^2 / (2 sigma^2)). Dense fp32 / fp64 GPU inputs: one GEMM
     (hipBLASLt) and the in-place HIP epilogue ``csrc/kernelmat.hip`` (one pass instead of
-    five elementwise torch passes over the n x m block)."""
+    five elementwise torch passes over the n x m block). Both inputs sparse: the fused
+    CSR x CSR kernel of ``csrc/csr_kernel.hip``."""
+    if _sp(X) and _sp(Y):
+        return _sparse_block(X, Y, "rbf", sigma=sigma)
     dense = not (X.is_sparse or Y.is_sparse or X.layout == torch.sparse_csr or Y.layout == torch.sparse_csr)
     if (dense and X.device.type == "cuda" and X.dtype == Y.dtype and X.dtype in (torch.float32, torch.float64)
             and _lib.use_native(X)):

@@ -37,6 +37,13 @@ from ..parallel.comm import Communicator
 from . import kernels as KF
 
 
+PREDICT_TILE_BYTES = 1 << 28  # kernel block of one query tile against the union of the SVs
+
+
+def _sparse(X) -> bool:
+    return X.is_sparse or X.layout == torch.sparse_csr
+
+
 def kernel_matrix(X, Y, kernel: str = "linear", sigma: float = 1.0, k: float = 1.0, b: float = 0.0):
     if kernel == "linear":
         return KF.linear_kernel(X, Y, k, b)
@@ -233,8 +240,9 @@ class BinarySVM:
             G += yv * (yi * dai * K[i] + yj * daj * K[j])
         return self._finish(Xd, yv, a, G, it)
 
-    def _finish(self, Xd, yv, a, G, steps: int) -> "BinarySVM":
-        """Bias from the free SVs (or the violating-pair midpoint) and the SV set."""
+    def _finish(self, Xd, yv, a, G, steps: int, rows: Optional[torch.Tensor] = None) -> "BinarySVM":
+        """Bias from the free SVs (or the violating-pair midpoint) and the SV set. ``rows``
+        (sparse ``Xd`` only): the machine's rows of ``Xd``; the SVs stay a CSR tensor."""
         Cc = self.C
         pos = yv > 0
         self.n_iterations = steps + 1
@@ -253,7 +261,12 @@ class BinarySVM:
         self.bias = -rho
         sv = a > 1e-12
         self.sv_index = torch.nonzero(sv).reshape(-1)
-        self.sv = Xd.to_dense()[sv] if (Xd.is_sparse or Xd.layout == torch.sparse_csr) else Xd[sv]
+        if _sparse(Xd):
+            from ..ops import csr_kernel as CK
+
+            self.sv = CK.take_rows(Xd, self.sv_index if rows is None else rows.to(self.sv_index.device)[self.sv_index])
+        else:
+            self.sv = Xd[sv]
         self.coef = (a * yv)[sv]
         return self
 
@@ -281,7 +294,9 @@ class MultiClassSVM:
         yl = y.long().reshape(-1)
         Xd = X.double()
         Kfull = kernel_matrix(Xd, Xd, self.kw.get("kernel", "linear"), self.kw.get("sigma", 1.0))
-        Xdense = Xd.to_dense() if (Xd.is_sparse or Xd.layout == torch.sparse_csr) else Xd
+        sparse = _sparse(Xd)
+        for attr in ("sv_union", "sv_train_index", "coef_matrix", "biases"):
+            self.__dict__.pop(attr, None)
         pairs = []
         for a in range(self.K):
             for b in range(a + 1, self.K):
@@ -297,15 +312,73 @@ class MultiClassSVM:
                              proto.max_iter)
             if res is not None:
                 for (key, idx, yy), (al, G, steps) in zip(pairs, res):
-                    self.machines[key] = BinarySVM(**self.kw)._finish(Xdense[idx], yy.to(al.device), al, G, steps)
-                return self
+                    m = BinarySVM(**self.kw)
+                    self.machines[key] = (m._finish(Xd, yy.to(al.device), al, G, steps, rows=idx) if sparse
+                                          else m._finish(Xd[idx], yy.to(al.device), al, G, steps))
+                return self._pack(Xd, pairs) if sparse else self
         for key, idx, yy in pairs:
-            self.machines[key] = BinarySVM(**self.kw).fit(Xdense[idx], yy, Kfull[idx][:, idx])
+            if sparse:
+                from ..ops import csr_kernel as CK
+
+                self.machines[key] = BinarySVM(**self.kw).fit(CK.take_rows(Xd, idx), yy, Kfull[idx][:, idx])
+            else:
+                self.machines[key] = BinarySVM(**self.kw).fit(Xd[idx], yy, Kfull[idx][:, idx])
+        return self._pack(Xd, pairs) if sparse else self
+
+    def _pack(self, Xd, pairs):
+        """Sparse training set: every training row belongs to K - 1 machines, so the union of
+        the machines' support rows is stored once (CSR, with its training indices), next to a
+        coefficient matrix [n_union, n_machines] (zero for non-members) and the biases.
+        ``predict`` then needs one kernel block and one GEMM per query tile."""
+        from ..ops import csr_kernel as CK
+
+        train = [idx.to(self.machines[key].sv_index.device)[self.machines[key].sv_index] for key, idx, _ in pairs]
+        dev = train[0].device if train else Xd.device
+        union = torch.unique(torch.cat(train)) if train else torch.zeros(0, dtype=torch.long, device=dev)
+        coef = torch.zeros((union.numel(), len(pairs)), dtype=torch.float64, device=dev)
+        for q, ((key, _, _), rows) in enumerate(zip(pairs, train)):
+            coef[torch.searchsorted(union, rows), q] = self.machines[key].coef
+        self.sv_train_index, self.sv_union = union, CK.take_rows(Xd, union)
+        self.coef_matrix = coef
+        self.biases = torch.tensor([self.machines[key].bias for key, _, _ in pairs], dtype=torch.float64, device=dev)
+        self._pairs = [key for key, _, _ in pairs]
         return self
+
+    def decisions(self, X) -> torch.Tensor:
+        """Decision values ``[n, n_machines]`` of a sparse-trained model, machines in the order
+        of ``self.machines``: per query tile (its kernel block bounded by
+        ``PREDICT_TILE_BYTES``) one kernel block against the union of the SVs and one GEMM."""
+        n, nu = X.shape[0], self.sv_union.shape[0]
+        kernel, sigma = self.kw.get("kernel", "linear"), self.kw.get("sigma", 1.0)
+        step = max(1, PREDICT_TILE_BYTES // (8 * max(nu, 1)))
+        out = torch.empty((n, len(self._pairs)), dtype=torch.float64, device=self.coef_matrix.device)
+        Xq = X.double()
+        if _sparse(Xq):
+            from ..ops import csr_kernel as CK
+            from ..ops.csr_stats import to_csr_operand
+
+            Xq = to_csr_operand(Xq)
+        for a in range(0, n, step):
+            b = min(a + step, n)
+            if isinstance(Xq, torch.Tensor):
+                Kx = kernel_matrix(Xq[a:b], self.sv_union, kernel, sigma)
+            elif kernel == "linear":
+                Kx = CK.kernel_block(Xq, self.sv_union, "linear", rows=(a, b))
+            elif kernel == "rbf":
+                Kx = CK.kernel_block(Xq, self.sv_union, "rbf", sigma=sigma, rows=(a, b))
+            else:
+                raise ValueError(kernel)
+            out[a:b] = Kx @ self.coef_matrix + self.biases
+        return out
 
     def predict(self, X):
         votes = torch.zeros((X.shape[0], self.K), dtype=torch.float64, device=X.device)
         ar = torch.arange(X.shape[0], device=X.device)
+        if hasattr(self, "sv_union"):
+            D = self.decisions(X)
+            for q, (a, b) in enumerate(self._pairs):
+                votes[ar, torch.where(D[:, q] > 0, a, b)] += 1
+            return votes.argmax(1)
         for (a, b), m in self.machines.items():
             win = torch.where(m.decision(X) > 0, a, b)
             votes[ar, win] += 1
