@@ -54,32 +54,6 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
   return z ^ (z >> 31);
 }
 
-// wave64 inclusive prefix sum on the DPP network (no LDS round trips): Hillis-Steele
-// within each 16-lane row (row_shr 1, 2, 4, 8), then row_bcast:15 into rows 1 and 3
-// and row_bcast:31 into rows 2 and 3. Lanes without a source add 0 (old = 0).
-__device__ __forceinline__ float dpp_add(float v, int ctrl_sel) {
-  int t;
-  switch (ctrl_sel) {
-    case 0: t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xf, 0xf, false); break;
-    case 1: t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xf, 0xf, false); break;
-    case 2: t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xf, 0xf, false); break;
-    case 3: t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xf, 0xf, false); break;
-    case 4: t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xa, 0xf, false); break;
-    default: t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xc, 0xf, false); break;
-  }
-  return v + __int_as_float(t);
-}
-
-__device__ __forceinline__ float wave_incl_scan(float v, int) {
-  v = dpp_add(v, 0);
-  v = dpp_add(v, 1);
-  v = dpp_add(v, 2);
-  v = dpp_add(v, 3);
-  v = dpp_add(v, 4);
-  v = dpp_add(v, 5);
-  return v;
-}
-
 // a relaxed device-scope atomic add by ONE lane at a uniform row base + a byte offset that is
 // laundered into a VGPR: a uniform address would be rewritten into a wave reduction (mbcnt,
 // popcount and two branches around the atomic) although only one lane is active, and a
@@ -219,19 +193,21 @@ struct DocRow<unsigned char> {
 
 // Fused parameter-server rows (push-pull with sparse rows, models/lda.py): the word rows
 // are read straight from the PULL payload (slot of local row w at pull_off[w], capacity
-// pull_cap[w]; parallel/sparse_ps.py layout, csrc/rowcodec.hip slot format) into the wave's
+// pull_cap[w]; parallel/sparse_ps.py layout, csrc/ps_slot.h slot format) into the wave's
 // LDS row, and a chunk's word-row delta is written straight into the PUSH payload slot
 // (dense slot: atomic adds; sparse slot: one reservation per wave on the slot's nnz word,
 // entries of several chunks of one word may repeat a topic -- the owner's decode_add sums
 // them). No dense local table is materialised, decoded or re-encoded.
-struct PsRows {
-  const unsigned char* pbuf;
-  const long* poff;
-  const int* pcap;
-  unsigned char* qbuf;
-  const long* qoff;
-  const int* qcap;
-  int* overflow;
+// The samplers spell the slot layout of ps_slot.h out as raw pointer expressions: its
+// accessors change the code generation of every sampler kernel, which has not been timed.
+struct PsRows {  // (PsRows{}: no parameter server, the local word table)
+  const unsigned char* pbuf = nullptr;
+  const long* poff = nullptr;
+  const int* pcap = nullptr;
+  unsigned char* qbuf = nullptr;
+  const long* qoff = nullptr;
+  const int* qcap = nullptr;
+  int* overflow = nullptr;
 };
 
 // Dense sampler: one wave per word chunk, the word's factors qw in registers (TPL topics per
@@ -467,7 +443,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6 + XW < 8 
         }
 #pragma unroll
         for (int t = 0; t < TPL; ++t) s = fmaf((float)((r[t >> 2] >> (8 * (t & 3))) & 0xFFu), qw[t], s);
-        const float incl = wave_incl_scan(s, lane);
+        const float incl = wave_scan_incl(s);
         const float total = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(incl), 63));
         // 32-bit hash of (chunk key, index): a few scalar instructions (the loop issues about
         // as many SALU as VALU instructions, both pipes ~70 % busy)
@@ -492,10 +468,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6 + XW < 8 
           const unsigned char* xb = (const unsigned char*)(xr + TPL);
           const float own = src == zl && lane == zt ? 1.f : 0.f;
           const float pv = lane < TPL ? ((float)xb[lane] - own + alpha) * xr[lane] : 0.f;
-          float c = dpp_add(pv, 0);
-          c = dpp_add(c, 1);
-          c = dpp_add(c, 2);
-          c = dpp_add(c, 3);
+          float c = dpp_shift_add(pv, 0);
+          c = dpp_shift_add(c, 1);
+          c = dpp_shift_add(c, 2);
+          c = dpp_shift_add(c, 3);
           const unsigned long long h = __builtin_amdgcn_ballot_w64(c + ex > u) & ((1ull << TPL) - 1);
           const unsigned long long nzp = __builtin_amdgcn_ballot_w64(pv > 0.f) & ((1ull << TPL) - 1);
           found = h ? (int)__builtin_ctzll(h) : (nzp ? 63 - (int)__builtin_clzll(nzp) : TPL - 1);
@@ -573,7 +549,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6 + XW < 8 
         float s = alpha * qs;
   #pragma unroll
         for (int t = 0; t < TPL; ++t) s = fmaf(nd[t], qw[t], s);
-        const float incl = wave_incl_scan(s, lane);
+        const float incl = wave_scan_incl(s);
         const float total = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(incl), 63));
         const unsigned long long rbits = mix64(seed ^ ((unsigned long long)i * 0xD6E8FEB86659FD93ull));
         const float u = ((float)(unsigned)(rbits >> 40) * (1.f / 16777216.f)) * total;
@@ -598,10 +574,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6 + XW < 8 
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
           const float* xr = (const float*)s_x[wv];
           const float pv = lane < TPL ? (xr[lane] + alpha) * xr[TPL + lane] : 0.f;
-          float c = dpp_add(pv, 0);
-          c = dpp_add(c, 1);
-          c = dpp_add(c, 2);
-          c = dpp_add(c, 3);  // inclusive prefix over lanes 0..15 (one DPP row)
+          float c = dpp_shift_add(pv, 0);
+          c = dpp_shift_add(c, 1);
+          c = dpp_shift_add(c, 2);
+          c = dpp_shift_add(c, 3);  // inclusive prefix over lanes 0..15 (one DPP row)
           const unsigned long long h = __ballot(lane < TPL && c + ex > u) & ((1ull << TPL) - 1);
           const unsigned long long nzp = __ballot(pv > 0.f) & ((1ull << TPL) - 1);
           found = h ? (int)__builtin_ctzll(h) : (nzp ? 63 - (int)__builtin_clzll(nzp) : TPL - 1);
@@ -671,7 +647,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6 + XW < 8 
 #pragma unroll
           for (int t = 0; t < TPL; ++t) mine += nw0s[t] != 0 ? 1 : 0;
         }
-        const float incl = wave_incl_scan((float)mine, lane);
+        const float incl = wave_scan_incl((float)mine);
         const int tot = (int)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(incl), 63));
         int base = 0;
         if (tot) {
@@ -889,7 +865,7 @@ __global__ __launch_bounds__(64 * WAVES) void lda_cgs_sparse_kernel(
       }
       int mine = 0;
       for (int t = t0; t < K; t += stride) mine += row[t] != 0 ? 1 : 0;
-      const float incl = wave_incl_scan((float)mine, lane);
+      const float incl = wave_scan_incl((float)mine);
       const int tot = (int)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(incl), 63));
       if (tot == 0) return;
       int base = 0;
@@ -985,14 +961,14 @@ __global__ __launch_bounds__(64 * WAVES) void lda_cgs_sparse_kernel(
     }
     __syncthreads();
     for (int k = wv; k < nb; k += WAVES) {
-      const float v = wave_incl_scan(s_qw[64 * k + lane], lane);
+      const float v = wave_scan_incl(s_qw[64 * k + lane]);
       if (lane == 63) s_bs[k] = v;
     }
     __syncthreads();
     if (wv == 0) {
       float v = 0.f;
       for (int k = lane; k < nb; k += 64) v += s_bs[k];
-      v = wave_incl_scan(v, lane);
+      v = wave_scan_incl(v);
       if (lane == 63) s_q = v;
     }
     __syncthreads();
@@ -1070,7 +1046,7 @@ __global__ __launch_bounds__(64 * WAVES) void lda_cgs_sparse_kernel(
       long sp2 = 0, pp2 = 0;
       int dd2 = 0, zz2 = 0;
       load_ids(i + 2 * WAVES, sp2, dd2, zz2, pp2);
-      const float inclb = wave_incl_scan(sb, lane);
+      const float inclb = wave_scan_incl(sb);
       const float B = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inclb), 63));
       const float corr = inv_z;
       const float A = alpha * fmaxf(uni_f(s_q) - corr, 0.f);
@@ -1144,7 +1120,7 @@ __global__ __launch_bounds__(64 * WAVES) void lda_cgs_sparse_kernel(
         const int zb6 = z >> 6;
         float sd = 0.f;
         for (int k = lane; k < nb; k += 64) sd += s_bs[k] - (k == zb6 ? corr : 0.f);
-        const float incld = wave_incl_scan(sd, lane);
+        const float incld = wave_scan_incl(sd);
         const unsigned long long hit = __ballot(incld > u2);
         const int src = hit ? (int)__builtin_ctzll(hit) : 63;
         int fb = nb - 1;
@@ -1163,7 +1139,7 @@ __global__ __launch_bounds__(64 * WAVES) void lda_cgs_sparse_kernel(
         base = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(base), src));
         const int t = 64 * fb + lane;
         const float q = t < K ? (t == z ? qz : s_qw[t]) : 0.f;
-        const float inclt = wave_incl_scan(q, lane) + base;
+        const float inclt = wave_scan_incl(q) + base;
         const unsigned long long h2 = __ballot(inclt > u2);
         const unsigned long long pos = __ballot(q > 0.f);
         const int s2 = h2 ? (int)__builtin_ctzll(h2) : (pos ? 63 - (int)__builtin_clzll(pos) : 0);
@@ -1255,66 +1231,90 @@ __global__ __launch_bounds__(64 * WAVES) void lda_cgs_sparse_kernel(
 }  // namespace
 
 namespace {
+template <int V>
+using ic = std::integral_constant<int, V>;
+
+// The typed doc-topic rows for ndk_bits (32: int32 counts; 16: packed uint16; 8: packed uint8,
+// every doc < 256 tokens) handed to f, after the row type's ldd rule: a row stride of a whole
+// number of align_bytes (16: the dense sampler's dwordx4 row loads; 4: the dword atomics)
+template <class F>
+int with_doc_rows(void* ndk, int ldd, int ndk_bits, int align_bytes, F&& f) {
+  auto typed = [&](auto* rows) { return ldd % (align_bytes / (int)sizeof(*rows)) ? HARP_EBADARG : f(rows); };
+  switch (ndk_bits) {
+    case 32: return typed((int*)ndk);
+    case 16: return typed((unsigned short*)ndk);
+    case 8: return typed((unsigned char*)ndk);
+  }
+  return HARP_EBADARG;
+}
+
 // workgroups of the dense sampler resident at once on this device (occupancy x CUs)
-template <class DT, int XW>
-long resident_blocks(int K) {
-  static long cached[3] = {0, 0, 0};
-  const int slot = K <= 256 ? 0 : K <= 512 ? 1 : 2;
-  if (cached[slot]) return cached[slot];
+template <int TPL, class DT, int XW>
+long resident_blocks() {
+  static long cached = 0;
+  if (cached) return cached;
   int dev = 0, cus = 0, per = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     return 0;
-  hipError_t e = slot == 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, lda_cgs_kernel<4, DT, XW>, 256, 0)
-                 : slot == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, lda_cgs_kernel<8, DT, XW>, 256, 0)
-                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, lda_cgs_kernel<16, DT, XW>, 256, 0);
-  if (e != hipSuccess || per <= 0) return 0;
-  cached[slot] = (long)per * cus;
-  return cached[slot];
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, lda_cgs_kernel<TPL, DT, XW>, 256, 0) != hipSuccess || per <= 0)
+    return 0;
+  cached = (long)per * cus;
+  return cached;
 }
 
-template <class DT, int XW = 0>
+template <class DT, int XW>
 int launch_cgs(const int* tdoc, const int* tword, int* tz, const long* chunk_start, long nchunks, DT* ndk, int ldd,
                int* nwk, int ldw, const float* inv_nk, int* nk_delta, int K, float alpha, float beta,
                unsigned long long seed, int det, PsRows ps, const long* lpt, hipStream_t s) {
-  long blocks = (nchunks + 3) / 4;  // 4 waves per block
-  if (blocks > 8192) blocks = 8192;
-  if (lpt && !det) {  // the snake deal assumes every wave is resident: one wave per slot
-    const long res = resident_blocks<DT, XW>(K);
-    if (res > 0 && blocks > res) blocks = res;
-  }
-  if (det) blocks = 1;
-  const dim3 g((unsigned)blocks), bl(256);
-  if (K <= 256) {
-    if (ldd < 256 || ldw < 256) return HARP_EBADARG;
-    lda_cgs_kernel<4, DT, XW><<<g, bl, 0, s>>>(tdoc, tword, tz, chunk_start, nchunks, ndk, ldd, nwk, ldw, inv_nk,
-                                           nk_delta, K, alpha, beta, seed, det, ps, lpt);
-  } else if (K <= 512) {
-    if (ldd < 512 || ldw < 512) return HARP_EBADARG;
-    lda_cgs_kernel<8, DT, XW><<<g, bl, 0, s>>>(tdoc, tword, tz, chunk_start, nchunks, ndk, ldd, nwk, ldw, inv_nk,
-                                           nk_delta, K, alpha, beta, seed, det, ps, lpt);
-  } else {
-    if (ldd < 1024 || ldw < 1024) return HARP_EBADARG;
-    lda_cgs_kernel<16, DT, XW><<<g, bl, 0, s>>>(tdoc, tword, tz, chunk_start, nchunks, ndk, ldd, nwk, ldw, inv_nk,
-                                            nk_delta, K, alpha, beta, seed, det, ps, lpt);
-  }
-  return harp_launch_status();
+  auto run = [&](auto tpl) {  // K_pad = 64 topics per lane
+    constexpr int TPL = decltype(tpl)::value;
+    long blocks = (nchunks + 3) / 4;  // 4 waves per block
+    if (blocks > 8192) blocks = 8192;
+    if (lpt && !det) {  // the snake deal assumes every wave is resident: one wave per slot
+      const long res = resident_blocks<TPL, DT, XW>();
+      if (res > 0 && blocks > res) blocks = res;
+    }
+    if (det) blocks = 1;
+    if (ldd < 64 * TPL || ldw < 64 * TPL) return HARP_EBADARG;
+    lda_cgs_kernel<TPL, DT, XW><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(
+        tdoc, tword, tz, chunk_start, nchunks, ndk, ldd, nwk, ldw, inv_nk, nk_delta, K, alpha, beta, seed, det, ps, lpt);
+    return harp_launch_status();
+  };
+  return K <= 256 ? run(ic<4>{}) : K <= 512 ? run(ic<8>{}) : run(ic<16>{});
 }
-}  // namespace
 
 // ndk_bits: 32 -> int32 doc-topic counts; 16 -> packed uint16 (ldd multiple of 8); 8 -> packed
 // uint8 (every doc < 256 tokens; ldd multiple of 16)
 // variant: 0 = compiler occupancy, 3 = two more waves per SIMD (fewer VGPRs, some spilled)
-static int lda_cgs_impl(const int* tdoc, const int* tword, int* tz, const long* chunk_start, long nchunks, void* ndk,
-                        int ldd, int ndk_bits, int* nwk, int ldw, const float* inv_nk, int* nk_delta, int K, float alpha,
-                        float beta, unsigned long long seed, int variant, PsRows ps, const long* lpt, hipStream_t s);
+int lda_cgs_impl(const int* tdoc, const int* tword, int* tz, const long* chunk_start, long nchunks, void* ndk, int ldd,
+                 int ndk_bits, int* nwk, int ldw, const float* inv_nk, int* nk_delta, int K, float alpha, float beta,
+                 unsigned long long seed, int variant, PsRows ps, const long* lpt, hipStream_t s) {
+  if (nchunks <= 0) return HARP_OK;
+  // variant 0: six waves per SIMD; 3: seven (the default). Round 1's variants (1: a
+  // float-row prefetch; 2, 4, 5: other forced occupancies) measured slower
+  // (profiles/r1_lda/occupancy) and are no longer built.
+  // variant | 0x100: deterministic one-wave sampling in chunk order (tests); | 0x200: one
+  // wave in the chunk-descriptor order of lpt (tests of the production schedule)
+  const int det = (variant & 0x200) ? 2 : (variant & 0x100) ? 1 : 0;
+  variant &= 0xff;
+  if (K <= 0 || K > 1024 || ldw % 4 || (variant != 0 && variant != 3)) return HARP_EBADARG;
+  return with_doc_rows(ndk, ldd, ndk_bits, 16, [&](auto* rows) {
+    auto go = [&](auto xw) {
+      return launch_cgs<std::remove_pointer_t<decltype(rows)>, decltype(xw)::value>(
+          tdoc, tword, tz, chunk_start, nchunks, rows, ldd, nwk, ldw, inv_nk, nk_delta, K, alpha, beta, seed, det, ps,
+          lpt, s);
+    };
+    return variant == 3 ? go(ic<1>{}) : go(ic<0>{});
+  });
+}
+}  // namespace
 
 HARP_EXPORT int harp_lda_cgs(const int* tdoc, const int* tword, int* tz, const long* chunk_start, long nchunks,
                              void* ndk, int ldd, int ndk_bits, int* nwk, int ldw, const float* inv_nk, int* nk_delta,
                              int K, float alpha, float beta, unsigned long long seed, int variant, const long* lpt,
                              hipStream_t s) {
-  const PsRows none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   return lda_cgs_impl(tdoc, tword, tz, chunk_start, nchunks, ndk, ldd, ndk_bits, nwk, ldw, inv_nk, nk_delta, K, alpha,
-                      beta, seed, variant, none, lpt, s);
+                      beta, seed, variant, PsRows{}, lpt, s);
 }
 
 // The dense sampler on fused parameter-server rows (PsRows above): pull payload slots in,
@@ -1329,40 +1329,6 @@ HARP_EXPORT int harp_lda_cgs_ps(const int* tdoc, const int* tword, int* tz, cons
   int kp = K <= 256 ? 256 : K <= 512 ? 512 : 1024;
   return lda_cgs_impl(tdoc, tword, tz, chunk_start, nchunks, ndk, ldd, ndk_bits, nullptr, kp, inv_nk, nk_delta, K,
                       alpha, beta, seed, variant, ps, lpt, s);
-}
-
-static int lda_cgs_impl(const int* tdoc, const int* tword, int* tz, const long* chunk_start, long nchunks, void* ndk,
-                        int ldd, int ndk_bits, int* nwk, int ldw, const float* inv_nk, int* nk_delta, int K, float alpha,
-                        float beta, unsigned long long seed, int variant, PsRows ps, const long* lpt, hipStream_t s) {
-  if (nchunks <= 0) return HARP_OK;
-  // variant 0: six waves per SIMD; 3: seven (the default). Round 1's variants (1: a
-  // float-row prefetch; 2, 4, 5: other forced occupancies) measured slower
-  // (profiles/r1_lda/occupancy) and are no longer built.
-  // variant | 0x100: deterministic one-wave sampling in chunk order (tests); | 0x200: one
-  // wave in the chunk-descriptor order of lpt (tests of the production schedule)
-  const int det = (variant & 0x200) ? 2 : (variant & 0x100) ? 1 : 0;
-  variant &= 0xff;
-  if (K <= 0 || K > 1024 || ldw % 4 || (variant != 0 && variant != 3)) return HARP_EBADARG;
-#define CGS_ARGS tdoc, tword, tz, chunk_start, nchunks
-#define CGS_TAIL nwk, ldw, inv_nk, nk_delta, K, alpha, beta, seed, det, ps, lpt, s
-  if (ndk_bits == 32) {
-    if (ldd % 4) return HARP_EBADARG;
-    return variant == 3 ? launch_cgs<int, 1>(CGS_ARGS, (int*)ndk, ldd, CGS_TAIL)
-                        : launch_cgs<int, 0>(CGS_ARGS, (int*)ndk, ldd, CGS_TAIL);
-  }
-  if (ndk_bits == 16) {
-    if (ldd % 8) return HARP_EBADARG;
-    return variant == 3 ? launch_cgs<unsigned short, 1>(CGS_ARGS, (unsigned short*)ndk, ldd, CGS_TAIL)
-                        : launch_cgs<unsigned short, 0>(CGS_ARGS, (unsigned short*)ndk, ldd, CGS_TAIL);
-  }
-  if (ndk_bits == 8) {
-    if (ldd % 16) return HARP_EBADARG;
-    return variant == 3 ? launch_cgs<unsigned char, 1>(CGS_ARGS, (unsigned char*)ndk, ldd, CGS_TAIL)
-                        : launch_cgs<unsigned char, 0>(CGS_ARGS, (unsigned char*)ndk, ldd, CGS_TAIL);
-  }
-#undef CGS_ARGS
-#undef CGS_TAIL
-  return HARP_EBADARG;
 }
 
 namespace {
@@ -1381,14 +1347,21 @@ size_t sparse_lds_bytes(int Kp, int waves) {
   return (Kp <= 4096 ? 8 : 4) * (size_t)Kp +
          (wd == 1 ? 4 * (size_t)Kp * waves : wd == 2 ? 4 * (size_t)Kp : 4 * 64 * (size_t)waves);
 }
+// LDS-resident workgroups per CU
+long sparse_per_cu(int Kp, int waves) { return 163840 / ((long)sparse_lds_bytes(Kp, waves) + 1100); }
+// the smallest workgroup that still puts >= 24 waves on a CU
+int sparse_auto_waves(int K) {
+  const int Kp = (K + 63) / 64 * 64;
+  for (int w = 4; w <= 8; w *= 2)
+    if (sparse_per_cu(Kp, w) * w >= 24) return w;
+  return 16;
+}
 
-template <int WAVES, class DT, bool SPAN = false>
-int launch_sparse(const int* tdoc, const long* tspan, const int* tword, int* tz, const long* chunk_start, long nchunks,
-                  const int* order,
-                  int* work, const long* tpos,
+template <int WAVES, class DT, bool SPAN>
+int launch_sparse(int K, int det, const int* tdoc, const long* tspan, const int* tword, int* tz,
+                  const long* chunk_start, long nchunks, const int* order, int* work, const long* tpos,
                   const long* doc_off, unsigned short* zdoc, DT* ndk, int ldd, int* nwk, int ldw, const float* inv_nk,
-                  int* nk_delta, int K, float alpha, float beta, unsigned long long seed, int det, hipStream_t s,
-                  PsRows ps = PsRows{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}) {
+                  int* nk_delta, float alpha, float beta, unsigned long long seed, PsRows ps, hipStream_t s) {
   const int Kp = (K + 63) / 64 * 64;
   const int ldelta = Kp <= 4096;  // LDS topic-sum deltas while they cost at most 16 KB
   const int wdelta = sparse_wdelta(Kp);
@@ -1399,7 +1372,7 @@ int launch_sparse(const int* tdoc, const long* tspan, const int* tword, int* tz,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return HARP_ELAUNCH;
   // grid = resident workgroups (LDS- or wave-slot-bound), striding over the chunks
-  long per_cu = 163840 / (long)(lds + 1100);
+  long per_cu = sparse_per_cu(Kp, WAVES);
   if (per_cu > 32 / WAVES) per_cu = 32 / WAVES;
   if (per_cu < 1) per_cu = 1;
   long blocks = nchunks;
@@ -1410,11 +1383,36 @@ int launch_sparse(const int* tdoc, const long* tspan, const int* tword, int* tz,
       beta, seed, ldelta, wdelta, ps);
   return harp_launch_status();
 }
+
+// waves as the exports take it: the workgroup size in waves (1, 2, 4, 8 or 16), 0 = by K,
+// < 0 = one one-wave workgroup, bit-reproducible (tests); a: launch_sparse's arguments after det
+template <class DT, bool SPAN, class... A>
+int launch_sparse_waves(int waves, int K, A... a) {
+  const int det = waves < 0 ? 1 : 0;
+  if (det) waves = 1;
+  if (waves == 0) waves = sparse_auto_waves(K);
+  switch (waves) {
+    case 1: return launch_sparse<1, DT, SPAN>(K, det, a...);
+    case 2: return launch_sparse<2, DT, SPAN>(K, det, a...);
+    case 4: return launch_sparse<4, DT, SPAN>(K, det, a...);
+    case 16: return launch_sparse<16, DT, SPAN>(K, det, a...);
+  }
+  return launch_sparse<8, DT, SPAN>(K, det, a...);
+}
+
+// the span sampler on the local word table (nwk / ldw) or on fused parameter-server rows (ps)
+int sparse_span_impl(const long* tspan, const int* tword, int* tz, const long* chunk_start, long nchunks,
+                     const int* order, int* work, const long* tpos, unsigned short* zdoc, int* nwk, int ldw,
+                     const float* inv_nk, int* nk_delta, int K, float alpha, float beta, unsigned long long seed,
+                     int waves, PsRows ps, hipStream_t s) {
+  return launch_sparse_waves<int, true>(waves, K, nullptr, tspan, tword, tz, chunk_start, nchunks, order, work, tpos,
+                                        nullptr, zdoc, nullptr, 0, nwk, ldw, inv_nk, nk_delta, alpha, beta, seed, ps, s);
+}
 }  // namespace
 
 // Sparse-doc sampler (see lda_cgs_sparse_kernel): tpos[i] = doc-order position of token i
 // in zdoc (uint16 topics, doc_off[d] .. doc_off[d + 1] = doc d); ndk may be null (no
-// doc-topic counts kept); waves: workgroup size in waves (1, 2, 4, 8 or 16; 0 = by K); order: chunk
+// doc-topic counts kept); waves: launch_sparse_waves above; order: chunk
 // processing order (null = 0..nchunks-1); work: ONE int, zero on entry (chunk counter).
 HARP_EXPORT int harp_lda_cgs_sparse(const int* tdoc, const int* tword, int* tz, const long* chunk_start, long nchunks,
                                     const int* order, int* work, const long* tpos, const long* doc_off, unsigned short* zdoc, void* ndk, int ldd,
@@ -1422,48 +1420,11 @@ HARP_EXPORT int harp_lda_cgs_sparse(const int* tdoc, const int* tword, int* tz, 
                                     float alpha, float beta, unsigned long long seed, int waves, hipStream_t s) {
   if (nchunks <= 0) return HARP_OK;
   if (K <= 0 || K > kSparseMaxK || ldw < K || (ndk && ldd < K) || !tpos || !doc_off || !zdoc || !work) return HARP_EBADARG;
-  const int det = waves < 0 ? 1 : 0;  // waves < 0: one one-wave workgroup, bit-reproducible (tests)
-  if (det) waves = 1;
-  if (waves == 0) {  // auto: the smallest workgroup that still puts >= 24 waves on a CU
-    const int Kp = (K + 63) / 64 * 64;
-    waves = 16;
-    for (int w = 4; w <= 8; w *= 2) {
-      const long per_cu = 163840 / ((long)sparse_lds_bytes(Kp, w) + 1100);  // LDS-resident workgroups
-      if (per_cu * w >= 24) {
-        waves = w;
-        break;
-      }
-    }
-  }
-#define SP_ARGS tdoc, nullptr, tword, tz, chunk_start, nchunks, order, work, tpos, doc_off, zdoc
-#define SP_TAIL nwk, ldw, inv_nk, nk_delta, K, alpha, beta, seed, det, s
-  if (ndk_bits == 16) {
-    if (ldd % 2) return HARP_EBADARG;
-    unsigned short* n16 = (unsigned short*)ndk;
-    return waves == 1    ? launch_sparse<1>(SP_ARGS, n16, ldd, SP_TAIL)
-           : waves == 2  ? launch_sparse<2>(SP_ARGS, n16, ldd, SP_TAIL)
-           : waves == 4  ? launch_sparse<4>(SP_ARGS, n16, ldd, SP_TAIL)
-           : waves == 16 ? launch_sparse<16>(SP_ARGS, n16, ldd, SP_TAIL)
-                         : launch_sparse<8>(SP_ARGS, n16, ldd, SP_TAIL);
-  }
-  if (ndk_bits == 8) {
-    if (ldd % 4) return HARP_EBADARG;
-    unsigned char* n8 = (unsigned char*)ndk;
-    return waves == 1    ? launch_sparse<1>(SP_ARGS, n8, ldd, SP_TAIL)
-           : waves == 2  ? launch_sparse<2>(SP_ARGS, n8, ldd, SP_TAIL)
-           : waves == 4  ? launch_sparse<4>(SP_ARGS, n8, ldd, SP_TAIL)
-           : waves == 16 ? launch_sparse<16>(SP_ARGS, n8, ldd, SP_TAIL)
-                         : launch_sparse<8>(SP_ARGS, n8, ldd, SP_TAIL);
-  }
-  if (ndk_bits != 32) return HARP_EBADARG;
-  int* n32 = (int*)ndk;
-  return waves == 1    ? launch_sparse<1>(SP_ARGS, n32, ldd, SP_TAIL)
-         : waves == 2  ? launch_sparse<2>(SP_ARGS, n32, ldd, SP_TAIL)
-         : waves == 4  ? launch_sparse<4>(SP_ARGS, n32, ldd, SP_TAIL)
-         : waves == 16 ? launch_sparse<16>(SP_ARGS, n32, ldd, SP_TAIL)
-                       : launch_sparse<8>(SP_ARGS, n32, ldd, SP_TAIL);
-#undef SP_ARGS
-#undef SP_TAIL
+  return with_doc_rows(ndk, ldd, ndk_bits, 4, [&](auto* rows) {
+    return launch_sparse_waves<std::remove_pointer_t<decltype(rows)>, false>(
+        waves, K, tdoc, nullptr, tword, tz, chunk_start, nchunks, order, work, tpos, doc_off, zdoc, rows, ldd, nwk, ldw,
+        inv_nk, nk_delta, alpha, beta, seed, PsRows{}, s);
+  });
 }
 
 // The same sampler with per-token doc spans (tspan[i] = doc_off[d_i] | (len_i << 40)) in place
@@ -1475,34 +1436,14 @@ HARP_EXPORT int harp_lda_cgs_sparse_span(const long* tspan, const int* tword, in
                                          hipStream_t s) {
   if (nchunks <= 0) return HARP_OK;
   if (K <= 0 || K > kSparseMaxK || ldw < K || !tspan || !tpos || !zdoc || !work) return HARP_EBADARG;
-  const int det = waves < 0 ? 1 : 0;
-  if (det) waves = 1;
-  if (waves == 0) {
-    const int Kp = (K + 63) / 64 * 64;
-    waves = 16;
-    for (int w = 4; w <= 8; w *= 2) {
-      const long per_cu = 163840 / ((long)sparse_lds_bytes(Kp, w) + 1100);
-      if (per_cu * w >= 24) {
-        waves = w;
-        break;
-      }
-    }
-  }
-#define SS_ARGS nullptr, tspan, tword, tz, chunk_start, nchunks, order, work, tpos, nullptr, zdoc, (int*)nullptr, 0
-#define SS_TAIL nwk, ldw, inv_nk, nk_delta, K, alpha, beta, seed, det, s
-  return waves == 1    ? launch_sparse<1, int, true>(SS_ARGS, SS_TAIL)
-         : waves == 2  ? launch_sparse<2, int, true>(SS_ARGS, SS_TAIL)
-         : waves == 4  ? launch_sparse<4, int, true>(SS_ARGS, SS_TAIL)
-         : waves == 16 ? launch_sparse<16, int, true>(SS_ARGS, SS_TAIL)
-                       : launch_sparse<8, int, true>(SS_ARGS, SS_TAIL);
-#undef SS_ARGS
-#undef SS_TAIL
+  return sparse_span_impl(tspan, tword, tz, chunk_start, nchunks, order, work, tpos, zdoc, nwk, ldw, inv_nk, nk_delta, K,
+                          alpha, beta, seed, waves, PsRows{}, s);
 }
 
 // harp_lda_cgs_sparse_span with fused parameter-server rows: word rows come from the pull
 // payload slots (pbuf / poff / pcap, one per local row) and the sweep's word-row moves are
 // written into the zeroed push payload (qbuf / qoff / qcap); no dense word table. Slot
-// formats: parallel/sparse_ps.py, csrc/rowcodec.hip (K_pad ints per dense slot).
+// formats: parallel/sparse_ps.py, csrc/ps_slot.h (K_pad ints per dense slot).
 HARP_EXPORT int harp_lda_cgs_sparse_span_ps(const long* tspan, const int* tword, int* tz, const long* chunk_start,
                                             long nchunks, const int* order, int* work, const long* tpos,
                                             unsigned short* zdoc, const float* inv_nk, int* nk_delta, int K,
@@ -1513,50 +1454,20 @@ HARP_EXPORT int harp_lda_cgs_sparse_span_ps(const long* tspan, const int* tword,
   if (nchunks <= 0) return HARP_OK;
   if (K <= 0 || K > kSparseMaxK || !tspan || !tpos || !zdoc || !work) return HARP_EBADARG;
   if (!pbuf || !poff || !pcap || !qbuf || !qoff || !qcap || !overflow) return HARP_EBADARG;
-  const PsRows ps{pbuf, poff, pcap, qbuf, qoff, qcap, overflow};
-  const int det = waves < 0 ? 1 : 0;
-  if (det) waves = 1;
-  if (waves == 0) {
-    const int Kp = (K + 63) / 64 * 64;
-    waves = 16;
-    for (int w = 4; w <= 8; w *= 2) {
-      const long per_cu = 163840 / ((long)sparse_lds_bytes(Kp, w) + 1100);
-      if (per_cu * w >= 24) {
-        waves = w;
-        break;
-      }
-    }
-  }
-#define SS_ARGS nullptr, tspan, tword, tz, chunk_start, nchunks, order, work, tpos, nullptr, zdoc, (int*)nullptr, 0
-#define SS_TAIL nullptr, 0, inv_nk, nk_delta, K, alpha, beta, seed, det, s, ps
-  return waves == 1    ? launch_sparse<1, int, true>(SS_ARGS, SS_TAIL)
-         : waves == 2  ? launch_sparse<2, int, true>(SS_ARGS, SS_TAIL)
-         : waves == 4  ? launch_sparse<4, int, true>(SS_ARGS, SS_TAIL)
-         : waves == 16 ? launch_sparse<16, int, true>(SS_ARGS, SS_TAIL)
-                       : launch_sparse<8, int, true>(SS_ARGS, SS_TAIL);
-#undef SS_ARGS
-#undef SS_TAIL
+  return sparse_span_impl(tspan, tword, tz, chunk_start, nchunks, order, work, tpos, zdoc, nullptr, 0, inv_nk, nk_delta,
+                          K, alpha, beta, seed, waves, PsRows{pbuf, poff, pcap, qbuf, qoff, qcap, overflow}, s);
 }
 
+// (any ndk_bits other than 16 and 8 counts into int32 rows)
 HARP_EXPORT int harp_lda_count(const int* tdoc, const int* tword, const int* tz, long n, void* ndk, int ldd,
                                int ndk_bits, int* nwk, int ldw, int* nk, hipStream_t s) {
   if (n <= 0) return HARP_OK;
   long blocks = (n + 255) / 256;
   if (blocks > 65536) blocks = 65536;
-  if (ndk_bits == 16) {
-    if (ldd % 2) return HARP_EBADARG;
-    lda_count_kernel<unsigned short><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(tdoc, tword, tz, n,
-                                                                                  (unsigned short*)ndk, ldd, nwk, ldw,
-                                                                                  nk);
-  } else if (ndk_bits == 8) {
-    if (ldd % 4) return HARP_EBADARG;
-    lda_count_kernel<unsigned char><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(tdoc, tword, tz, n,
-                                                                                 (unsigned char*)ndk, ldd, nwk, ldw, nk);
-  } else {
-    lda_count_kernel<int><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(tdoc, tword, tz, n, (int*)ndk, ldd, nwk, ldw,
-                                                                       nk);
-  }
-  return harp_launch_status();
+  return with_doc_rows(ndk, ldd, ndk_bits == 16 || ndk_bits == 8 ? ndk_bits : 32, 4, [&](auto* rows) {
+    lda_count_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(tdoc, tword, tz, n, rows, ldd, nwk, ldw, nk);
+    return harp_launch_status();
+  });
 }
 
 #ifdef HARP_LDA_STAMPS

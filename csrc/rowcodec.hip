@@ -6,13 +6,8 @@
 // :429 with sparse TopicCountList rows, ml/java/.../lda/LDAUtil.java:159-213). Word-topic
 // rows are mostly zero, so over point-to-point xGMI the dense rows are link-bound.
 //
-// Payload of one peer = a sequence of per-row SLOTS at static byte offsets. A slot's
-// capacity comes from token totals that never change during sampling (pull: min(K, global
-// tokens of the word); push delta: min(K, 2 x local tokens)), so both ends derive the same
-// layout once and every call is a fixed-size all-to-all with no size exchange and no host
-// sync. A slot is
-//   sparse (cap >= 0): [int32 nnz][int32 counts cap][uint16 topics cap]   (4 + 6 cap bytes, 4-aligned)
-//   dense  (cap <  0): [int32 row K]                      (16-aligned; when 4 + 6 cap >= 4 K)
+// Payload of one peer = a sequence of per-row SLOTS at static byte offsets, sparse
+// (nnz, counts, topics) or dense (the int32 row): the format and its accessors are in ps_slot.h.
 //
 // One wave per row (up to 4 per workgroup, fewer for K > 4096 so the LDS rows stay
 // within 64 KB; K <= 16384), the row staged once in LDS (4 KB at K = 1024):
@@ -27,16 +22,12 @@
 //                   re-encoded in place (no dense table, no encode pass for the pull)
 // Received payloads are bounds-checked (nnz clamped to the slot, topics < K).
 #include "common.h"
+#include "ps_slot.h"
 
 namespace {
 
 constexpr int kMaxWaves = 4;               // rows per workgroup (at most)
 constexpr int kLdsBudget = 64 * 1024;      // default dynamic-LDS limit per workgroup
-
-__device__ __forceinline__ const int* slot_counts(const unsigned char* slot) { return (const int*)(slot + 4); }
-__device__ __forceinline__ const unsigned short* slot_topics(const unsigned char* slot, int cap) {
-  return (const unsigned short*)(slot + 4 + 4 * (long)cap);
-}
 
 // stage one row (K ints, 16-B aligned rows: K % 4 == 0, ld % 4 == 0) into this wave's LDS row
 __device__ __forceinline__ void load_row(int* lrow, const int* __restrict__ g, int K, int lane) {
@@ -58,10 +49,9 @@ __device__ __forceinline__ void sub_slot(int* lrow, const unsigned char* slot, i
     }
     return;
   }
-  int nnz = *(const int*)slot;
-  nnz = nnz < 0 ? 0 : (nnz > cap ? cap : nnz);
-  const int* cnt = slot_counts(slot);
-  const unsigned short* top = slot_topics(slot, cap);
+  const int nnz = ps_slot::nnz(slot, cap);
+  const int* cnt = ps_slot::counts(slot);
+  const unsigned short* top = ps_slot::topics(slot, cap);
   for (int e = lane; e < nnz; e += 64) {  // topics are distinct within a slot: no LDS races
     const int t = top[e];
     if (t < K) lrow[t] -= cnt[e];
@@ -77,8 +67,6 @@ __device__ __forceinline__ void store_slot(const int* lrow, unsigned char* slot,
     for (int c = lane; c < K / 4; c += 64) s4[c] = l4[c];
     return;
   }
-  int* cnt = (int*)(slot + 4);
-  unsigned short* top = (unsigned short*)(slot + 4 + 4 * (long)cap);
   const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
   int base = 0;
   bool over = false;
@@ -88,16 +76,11 @@ __device__ __forceinline__ void store_slot(const int* lrow, unsigned char* slot,
     const unsigned long long m = __ballot(v != 0);
     if (v != 0) {
       const int pos = base + __popcll(m & below);
-      if (pos < cap) {
-        cnt[pos] = v;
-        top[pos] = (unsigned short)j;
-      } else {
-        over = true;
-      }
+      if (ps_slot::put(slot, cap, pos, j, v)) over = true;
     }
     base += __popcll(m);
   }
-  if (lane == 0) *(int*)slot = base < cap ? base : cap;
+  if (lane == 0) ps_slot::set_nnz(slot, cap, base);
   if (__ballot(over) && lane == 0) overflow[0] = 1;
 }
 
@@ -150,8 +133,6 @@ __global__ __launch_bounds__(kMaxWaves * 64) void rowcodec_encode_direct_kernel(
     }
     return;
   }
-  int* cnt = (int*)(slot + 4);
-  unsigned short* top = (unsigned short*)(slot + 4 + 4 * (long)c);
   int base = 0;
   bool over = false;
   for (int s0 = 0; s0 < K; s0 += 1024) {
@@ -166,18 +147,13 @@ __global__ __launch_bounds__(kMaxWaves * 64) void rowcodec_encode_direct_kernel(
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       if (v[e] != 0) {
-        if (pos < c) {
-          cnt[pos] = v[e];
-          top[pos] = (unsigned short)(t0 + e);
-        } else {
-          over = true;
-        }
+        if (ps_slot::put(slot, c, pos, t0 + e, v[e])) over = true;
         ++pos;
       }
     }
     base += (int)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(incl), 63));
   }
-  if (lane == 0) *(int*)slot = base < c ? base : c;
+  if (lane == 0) ps_slot::set_nnz(slot, c, base);
   if (__ballot(over) && lane == 0) overflow[0] = 1;
 }
 
@@ -217,10 +193,9 @@ __global__ __launch_bounds__(kMaxWaves * 64) void rowcodec_decode_replace_kernel
   }
   __syncthreads();
   if (live && c >= 0) {
-    int nnz = *(const int*)slot;
-    nnz = nnz < 0 ? 0 : (nnz > c ? c : nnz);
-    const int* cnt = slot_counts(slot);
-    const unsigned short* top = slot_topics(slot, c);
+    const int nnz = ps_slot::nnz(slot, c);
+    const int* cnt = ps_slot::counts(slot);
+    const unsigned short* top = ps_slot::topics(slot, c);
     for (int e = lane; e < nnz; e += 64) {
       const int t = top[e];
       if (t < K) lrow[t] = cnt[e];
@@ -250,10 +225,9 @@ __global__ __launch_bounds__(kMaxWaves * 64) void rowcodec_decode_add_kernel(
     }
     return;
   }
-  int nnz = *(const int*)slot;
-  nnz = nnz < 0 ? 0 : (nnz > c ? c : nnz);
-  const int* cnt = slot_counts(slot);
-  const unsigned short* top = slot_topics(slot, c);
+  const int nnz = ps_slot::nnz(slot, c);
+  const int* cnt = ps_slot::counts(slot);
+  const unsigned short* top = ps_slot::topics(slot, c);
   for (int e = lane; e < nnz; e += 64) {
     const int t = top[e];
     if (t < K) atomicAdd(d + t, cnt[e]);
@@ -288,10 +262,9 @@ __global__ __launch_bounds__(kMaxWaves * 64) void rowcodec_decode_add16_kernel(
     }
     return;
   }
-  int nnz = *(const int*)slot;
-  nnz = nnz < 0 ? 0 : (nnz > c ? c : nnz);
-  const int* cnt = slot_counts(slot);
-  const unsigned short* top = slot_topics(slot, c);
+  const int nnz = ps_slot::nnz(slot, c);
+  const int* cnt = ps_slot::counts(slot);
+  const unsigned short* top = ps_slot::topics(slot, c);
   for (int e = lane; e < nnz; e += 64) {
     const int t = top[e], v = cnt[e];
     if (v && t < K) add16(d, t, v);
@@ -316,13 +289,12 @@ __global__ __launch_bounds__(kMaxWaves * 64) void rowcodec_copy_slots_kernel(
     for (int q = lane; q < K / 4; q += 64) d4[q] = a4[q];
     return;
   }
-  int nnz = *(const int*)a;
-  nnz = nnz < 0 ? 0 : (nnz > c ? c : nnz);
-  if (lane == 0) *(int*)d = nnz;
-  const int* ac = slot_counts(a);
-  int* dc = (int*)(d + 4);
-  const unsigned short* at = slot_topics(a, c);
-  unsigned short* dt = (unsigned short*)(d + 4 + 4 * (long)c);
+  const int nnz = ps_slot::nnz(a, c);
+  if (lane == 0) *ps_slot::nnz_word(d) = nnz;
+  const int* ac = ps_slot::counts(a);
+  int* dc = ps_slot::counts(d);
+  const unsigned short* at = ps_slot::topics(a, c);
+  unsigned short* dt = ps_slot::topics(d, c);
   for (int e = lane; e < nnz; e += 64) {
     dc[e] = ac[e];
     dt[e] = at[e];
@@ -352,10 +324,9 @@ __device__ __forceinline__ void merge_entries(const unsigned char* slot, int c, 
                                               const long* __restrict__ in_off, const int* __restrict__ in_cap, int K,
                                               int lane, F&& f, int stride = 64) {
   if (c >= 0) {
-    int nnz = *(const int*)slot;
-    nnz = nnz < 0 ? 0 : (nnz > c ? c : nnz);
-    const int* ocn = slot_counts(slot);
-    const unsigned short* otp = slot_topics(slot, c);
+    const int nnz = ps_slot::nnz(slot, c);
+    const int* ocn = ps_slot::counts(slot);
+    const unsigned short* otp = ps_slot::topics(slot, c);
     for (int e = lane; e < nnz; e += stride) {
       const int t = otp[e];
       if (t < K) f(t, ocn[e]);
@@ -371,10 +342,9 @@ __device__ __forceinline__ void merge_entries(const unsigned char* slot, int c, 
         if (v) f(t, v);
       }
     } else {
-      int nz = *(const int*)ds;
-      nz = nz < 0 ? 0 : (nz > dc ? dc : nz);
-      const int* dcn = slot_counts(ds);
-      const unsigned short* dtp = slot_topics(ds, dc);
+      const int nz = ps_slot::nnz(ds, dc);
+      const int* dcn = ps_slot::counts(ds);
+      const unsigned short* dtp = ps_slot::topics(ds, dc);
       for (int e = lane; e < nz; e += stride) {
         const int t = dtp[e], v = dcn[e];
         if (v && t < K) f(t, v);
@@ -441,10 +411,9 @@ __global__ __launch_bounds__(256) void rowcodec_merge_group_kernel(
         if (v) add(t, v);
       }
     } else {
-      int nz = *(const int*)ds;
-      nz = nz < 0 ? 0 : (nz > dc ? dc : nz);
-      const int* dcn = slot_counts(ds);
-      const unsigned short* dtp = slot_topics(ds, dc);
+      const int nz = ps_slot::nnz(ds, dc);
+      const int* dcn = ps_slot::counts(ds);
+      const unsigned short* dtp = ps_slot::topics(ds, dc);
       for (int e = gl; e < nz; e += G) {
         const int t = dtp[e], v = dcn[e];
         if (v && t < K) add(t, v);
@@ -460,10 +429,9 @@ __global__ __launch_bounds__(256) void rowcodec_merge_group_kernel(
     if (j + stride < nrows) mn = meta[j + stride];  // in flight during this row
     unsigned char* slot = canon + m.off;
     const int c = m.cap;  // >= 0: these classes are sparse rows
-    int nnz = *(const int*)slot;
-    nnz = nnz < 0 ? 0 : (nnz > c ? c : nnz);
-    int* ocn = (int*)(slot + 4);
-    unsigned short* otp = (unsigned short*)(slot + 4 + 4 * (long)c);
+    const int nnz = ps_slot::nnz(slot, c);
+    const int* ocn = ps_slot::counts(slot);
+    const unsigned short* otp = ps_slot::topics(slot, c);
     for (int e = gl; e < nnz; e += G) {
       const int t = otp[e];
       if (t < K) add(t, ocn[e]);
@@ -480,18 +448,13 @@ __global__ __launch_bounds__(256) void rowcodec_merge_group_kernel(
       const unsigned long long mk = (__ballot(keep) >> gshift) & gmask;  // this row's G lanes
       if (keep) {
         const int pos = base + __popcll(mk & below);
-        if (pos < c) {
-          ocn[pos] = v;
-          otp[pos] = (unsigned short)t;
-        } else {
-          over = true;
-        }
+        if (ps_slot::put(slot, c, pos, t, v)) over = true;
       }
       base += __popcll(mk);
       hk[i] = -1;
       hv[i] = 0;
     }
-    if (gl == 0) *(int*)slot = base < c ? base : c;
+    if (gl == 0) ps_slot::set_nnz(slot, c, base);
     m = mn;
   }
   if (over) atomicOr(overflow, 1);
@@ -524,8 +487,6 @@ __global__ __launch_bounds__(kMaxWaves * 64) void rowcodec_merge_kernel(
       atomicAdd(&acc[t], v);
       atomicOr(&bits[t >> 5], 1u << (t & 31));
     });
-    int* ocn = (int*)(slot + 4);
-    unsigned short* otp = (unsigned short*)(slot + 4 + 4 * (long)c);
     // compaction in topic order: lane L scans bitmap word wb + L (32 topics)
     int base = 0;
     for (int wb = 0; wb < nbw; wb += 64) {
@@ -543,12 +504,7 @@ __global__ __launch_bounds__(kMaxWaves * 64) void rowcodec_merge_kernel(
         const int t = (wi << 5) + __builtin_ctz(mm);
         const int v = acc[t];
         if (v != 0) {
-          if (pos < c) {
-            ocn[pos] = v;
-            otp[pos] = (unsigned short)t;
-          } else {
-            over = true;
-          }
+          if (ps_slot::put(slot, c, pos, t, v)) over = true;
           ++pos;
         }
         acc[t] = 0;
@@ -556,7 +512,7 @@ __global__ __launch_bounds__(kMaxWaves * 64) void rowcodec_merge_kernel(
       if (wi < nbw) bits[wi] = 0u;
       base += (int)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(incl), 63));
     }
-    if (lane == 0) *(int*)slot = base < c ? base : c;
+    if (lane == 0) ps_slot::set_nnz(slot, c, base);
   }
   if (__ballot(over) && lane == 0) atomicOr(overflow, 1);
   if (__ballot(neg) && lane == 0) atomicOr(overflow, 2);

@@ -323,3 +323,167 @@ def test_lda_budget_tuner_sparse_sampler_gpu(cuda):
     assert pct[0] == pytest.approx(100.0)
     assert any(40 <= p <= 80 for p in pct[1:4]), (pct, m.tuner.history)
     assert int(m.nk.sum()) == toks[0].numel()
+
+
+# ---- every dispatch arm of csrc/lda.hip's launchers, on one tiny corpus -----------------
+
+_ARM_DOCS, _ARM_WORDS, _ARM_TOKENS = 64, 48, 4096
+
+
+@pytest.fixture(scope="module")
+def arm_corpus(cuda):
+    """64 docs x 48 words, 4096 word-sorted tokens in chunks of at most 64 (about two per
+    word); read-only: every test samples on copies."""
+    from harp_amd.ops import lda as L
+
+    g = torch.Generator(device=cuda).manual_seed(17)
+    tdoc = torch.randint(0, _ARM_DOCS, (_ARM_TOKENS,), generator=g, device=cuda, dtype=torch.int32)
+    tword = torch.sort(torch.randint(0, _ARM_WORDS, (_ARM_TOKENS,), generator=g, device=cuda, dtype=torch.int32)).values
+    u = torch.rand(_ARM_TOKENS, generator=g, device=cuda)
+    # uint8 doc rows need every doc shorter than 256 tokens
+    assert int(torch.bincount(tdoc, minlength=_ARM_DOCS).max()) < 256
+    return tdoc, tword, u, L.build_chunks(tword, 64)
+
+
+_DT = {8: torch.uint8, 16: torch.int16, 32: torch.int32}
+_DENSE_ARMS = [("dense", K, bits, v, None) for K in (64, 300, 1000) for bits in (8, 16, 32) for v in (0, 3)]
+_SPARSE_ARMS = [("sparse", 100, bits, w, None) for w in (1, 2, 4, 8, 16) for bits in (8, 16, 32)]
+# no doc-topic table: per-token doc spans (the span export) or doc ids -> doc_off (null ndk)
+_SPARSE_ARMS += [("sparse", K, None, w, span) for K, w in ((1100, 4), (4200, 8)) for span in (True, False)]
+
+
+@pytest.mark.parametrize("sampler,K,bits,knob,span", _DENSE_ARMS + _SPARSE_ARMS)
+def test_every_dispatch_arm_conserves_counts(cuda, arm_corpus, monkeypatch, sampler, K, bits, knob, span):
+    """One sweep through each launcher arm (dense: topics per lane x doc-row width x occupancy
+    variant; sparse: workgroup waves x doc-row width, and the three LDS modes with and without
+    doc spans): topics stay in [0, K), tokens move, and every count table equals a recount."""
+    from harp_amd.ops import lda as L
+
+    tdoc, tword, u, chunks = arm_corpus
+    sparse = sampler == "sparse"
+    if sparse:
+        monkeypatch.setattr(L, "SAMPLER", "sparse")
+        monkeypatch.setattr(L, "SPARSE_WAVES", knob)
+        if span is not None:
+            monkeypatch.setattr(L, "SPAN", span)
+    else:
+        monkeypatch.setattr(L, "SAMPLER_VARIANT", knob)
+    tz = (u * K).int().clamp_(max=K - 1)
+    Kp = L.padded_topics(K)
+    ndk = None if bits is None else torch.zeros((_ARM_DOCS, Kp), dtype=_DT[bits], device=cuda)
+    nwk = torch.zeros((_ARM_WORDS, Kp), dtype=torch.int32, device=cuda)
+    nk = torch.zeros(Kp, dtype=torch.int32, device=cuda)
+    L.count(tdoc, tword, tz, ndk, nwk, nk)
+    di = L.DocIndex.build(tdoc, tz, _ARM_DOCS) if sparse else None
+    assert not sparse or span is None or (di.span is not None) == span
+    z0 = tz.clone()
+    d = L.cgs_sample(tdoc, tword, tz, chunks, ndk, nwk, nk, K, 0.1, 0.01, _ARM_WORDS * 0.01, 11, di)
+    torch.cuda.synchronize()
+    assert int(tz.min()) >= 0 and int(tz.max()) < K
+    assert (tz != z0).float().mean() > 0.2  # the sweep moved tokens
+    r_d = torch.zeros((_ARM_DOCS, Kp), dtype=torch.int32, device=cuda)
+    r_w = torch.zeros_like(nwk)
+    r_k = torch.zeros_like(nk)
+    L.count(tdoc, tword, tz, r_d, r_w, r_k)
+    if ndk is not None:
+        assert torch.equal(ndk.int() & (0xFFFF if bits == 16 else -1), r_d)
+    assert torch.equal(nwk, r_w)
+    assert torch.equal(nk + d, r_k)
+    if sparse:
+        assert torch.equal(di.zdoc[di.tpos].int() & 0xFFFF, tz)
+
+
+def test_bad_arguments_refused_before_any_launch(cuda, arm_corpus):
+    """The raw exports with valid buffers, one chunk and ONE bad argument each return 1 (bad
+    argument) and leave the topics and every table untouched; the same calls without the fault
+    return 0 and sample."""
+    from harp_amd.ops import _lib
+    from harp_amd.ops import lda as L
+
+    lib = _lib.kernels()
+    tdoc, tword, u, chunks = arm_corpus
+    K, Kp = 64, 1024  # (rows padded for any K <= 1024)
+    LD = Kp + 64  # the tables' row stride: a multiple of 16, so every fault below is the only one
+    tz = (u * K).int().clamp_(max=K - 1)
+    rows = {b: torch.zeros((_ARM_DOCS, LD), dtype=_DT[b], device=cuda) for b in (8, 16, 32)}
+    nwk = torch.zeros((_ARM_WORDS, LD), dtype=torch.int32, device=cuda)
+    nk = torch.zeros(Kp, dtype=torch.int32, device=cuda)
+    for b in (8, 16, 32):
+        L.count(tdoc, tword, tz, rows[b], nwk if b == 32 else None, nk if b == 32 else None)
+    di = L.DocIndex.build(tdoc, tz, _ARM_DOCS)
+    inv = torch.zeros(32768 + 64, dtype=torch.float32, device=cuda)
+    inv[:K] = 1.0 / (nk[:K].float() + _ARM_WORDS * 0.01)
+    delta = torch.zeros(32768 + 64, dtype=torch.int32, device=cuda)
+    work = torch.zeros(1, dtype=torch.int32, device=cuda)
+    order = torch.zeros(1, dtype=torch.int32, device=cuda)
+    # parameter-server payloads: one dense slot (cap < 0, Kp ints) per word, pull and push
+    pbuf = torch.zeros(_ARM_WORDS * Kp * 4, dtype=torch.uint8, device=cuda)
+    qbuf = torch.zeros_like(pbuf)
+    off = torch.arange(_ARM_WORDS, dtype=torch.int64, device=cuda) * (Kp * 4)
+    cap = torch.full((_ARM_WORDS,), -1, dtype=torch.int32, device=cuda)
+    over = torch.zeros(1, dtype=torch.int32, device=cuda)
+    if di.span is None:
+        lo = di.doc_off[tdoc.long()]
+        di.span = (lo | ((di.doc_off[tdoc.long() + 1] - lo) << 40)).contiguous()
+    state = [tz, *rows.values(), nwk, delta, work, di.zdoc, qbuf, over]
+    s = _lib.stream_ptr(cuda)
+    ps = dict(pbuf=pbuf.data_ptr(), poff=off.data_ptr(), pcap=cap.data_ptr(), qbuf=qbuf.data_ptr(),
+              qoff=off.data_ptr(), qcap=cap.data_ptr(), overflow=over.data_ptr())
+
+    def dense(K=K, bits=32, ldd=LD, ldw=LD, variant=3, **p):
+        if p:
+            p = {**ps, **p}
+            return lib.harp_lda_cgs_ps(tdoc.data_ptr(), tword.data_ptr(), tz.data_ptr(), chunks.data_ptr(), 1,
+                                       rows[bits].data_ptr(), ldd, bits, inv.data_ptr(), delta.data_ptr(), K, 0.1, 0.01,
+                                       11, variant, p["pbuf"], p["poff"], p["pcap"], p["qbuf"], p["qoff"], p["qcap"],
+                                       p["overflow"], None, s)
+        return lib.harp_lda_cgs(tdoc.data_ptr(), tword.data_ptr(), tz.data_ptr(), chunks.data_ptr(), 1,
+                                rows[bits].data_ptr(), ldd, bits, nwk.data_ptr(), ldw, inv.data_ptr(), delta.data_ptr(),
+                                K, 0.1, 0.01, 11, variant, None, s)
+
+    def sparse(entry, K=K, ldd=LD, ldw=LD, tpos=di.tpos.data_ptr(), work=work.data_ptr(), **p):
+        head = (tword.data_ptr(), tz.data_ptr(), chunks.data_ptr(), 1, order.data_ptr(), work, tpos)
+        tail = (K, 0.1, 0.01, 11, 4)
+        if entry == "ids":
+            return lib.harp_lda_cgs_sparse(tdoc.data_ptr(), *head, di.doc_off.data_ptr(), di.zdoc.data_ptr(),
+                                           rows[32].data_ptr(), ldd, 32, nwk.data_ptr(), ldw, inv.data_ptr(),
+                                           delta.data_ptr(), *tail, s)
+        if entry == "span":
+            return lib.harp_lda_cgs_sparse_span(di.span.data_ptr(), *head, di.zdoc.data_ptr(), nwk.data_ptr(), ldw,
+                                                inv.data_ptr(), delta.data_ptr(), *tail, s)
+        p = {**ps, **p}
+        return lib.harp_lda_cgs_sparse_span_ps(di.span.data_ptr(), *head, di.zdoc.data_ptr(), inv.data_ptr(),
+                                               delta.data_ptr(), *tail, p["pbuf"], p["poff"], p["pcap"], p["qbuf"],
+                                               p["qoff"], p["qcap"], p["overflow"], s)
+
+    faults = {
+        "K=0": lambda: dense(K=0), "K=1025": lambda: dense(K=1025), "ndk_bits=12": lambda: dense(bits=12),
+        "variant=1": lambda: dense(variant=1),
+        "ldd%4": lambda: dense(bits=32, ldd=LD + 2), "ldd%8": lambda: dense(bits=16, ldd=LD + 4),
+        "ldd%16": lambda: dense(bits=8, ldd=LD + 8), "ldw%4": lambda: dense(ldw=LD + 2),
+        "ldd<256": lambda: dense(K=64, ldd=128), "ldd<512": lambda: dense(K=300, ldd=256),
+        "ldd<1024": lambda: dense(K=1000, ldd=512),
+        "ps pbuf": lambda: dense(pbuf=None),
+    }
+    for e in ("ids", "span", "span_ps"):
+        faults[e + " K=32769"] = lambda e=e: sparse(e, K=32769, ldd=32832, ldw=32832)
+        faults[e + " tpos"] = lambda e=e: sparse(e, tpos=None)
+        faults[e + " work"] = lambda e=e: sparse(e, work=None)
+    for e in ("ids", "span"):
+        faults[e + " ldw<K"] = lambda e=e: sparse(e, ldw=32)
+    faults["span_ps pbuf"] = lambda: sparse("span_ps", pbuf=None)
+    # "ndk_bits=12" must not die on the Python side: rows has no key 12
+    rows[12] = rows[32]
+    before = [t.clone() for t in state]
+    got = {name: f() for name, f in faults.items()}
+    torch.cuda.synchronize()
+    assert got == {name: 1 for name in faults}
+    assert all(torch.equal(a, b) for a, b in zip(before, state))
+    # without the fault the same calls are accepted and sample
+    for ok in (dense, lambda: dense(pbuf=pbuf.data_ptr()), lambda: sparse("ids"), lambda: sparse("span"),
+               lambda: sparse("span_ps")):
+        z0 = tz.clone()
+        work.zero_()
+        assert ok() == 0
+        torch.cuda.synchronize()
+        assert not torch.equal(tz, z0)
