@@ -18,6 +18,7 @@ same parameters as named flags (which win when both are given):
             (ml/java subgraph/SCLauncher.java:76-88)                       [--strategy]
   ldacvb    <inputDir> <metafile> <outputDir> <numTerms> <numTopics> <numDocs> <maps> <iters>
             <threads> <mode>                 (contrib lda/LdaMapCollective.java, ldacvb.sh)
+            [--engine native|torch]   native (default): ops/lda_vb.py E-step, K <= 1024
   pagerank  <inputDir> <numUrls> <iters> <maps>   (contrib simplepagerank)
   daal      <algo> <maps> <threads> <memMB> <iters> <inputDir> <workDir> [algo args]
             (harp-daal-interface data_aux/Initialize.java:97-130 common prefix)
@@ -92,7 +93,7 @@ EXTRA = {  # named-only flags
     "subgraph": [("strategy", str, "allgather"), ("seed", int, 0)],
     "lda": [("vocab", int, 0)],
     "ldacvb": [("strategy", str, "allreduce"), ("init", str, "random"), ("alpha", float, 1e-3), ("eta", float, 0.0),
-               ("gamma_iters", int, 29)],
+               ("gamma_iters", int, 29), ("engine", str, "native")],
     "sgd": [("num_users", int, 0), ("num_items", int, 0)],
     "ccd": [("num_users", int, 0), ("num_items", int, 0)],
     "daal": [("k", int, 0), ("method", str, ""), ("label_cols", int, 1), ("n_trees", int, 50), ("max_depth", int, 10),
@@ -301,7 +302,7 @@ def _run_ldacvb(comm, cfg):
     # --init uniform also starts from its uniform beta (which keeps every topic identical)
     vc = LDAVBConfig(num_topics=cfg["num_topics"], iterations=cfg["iterations"], strategy=cfg["strategy"],
                      alpha=cfg["alpha"], eta=cfg["eta"], gamma_iters=cfg["gamma_iters"], gamma_tol=0.0,
-                     init=cfg["init"])
+                     init=cfg["init"], engine=cfg["engine"])
     res = train_lda_vb(comm, local, word, cnt, docs.numel(), vocab, vc)
     if comm.rank == 0:
         _write(os.path.join(cfg["output_dir"], "likelihood"),

@@ -16,6 +16,14 @@ statistics are accumulated by one scatter-add; the combine is ONE allreduce of t
 dense [K, V] matrix ("allreduce") or a push of word-block partitions to their owners +
 a pull of only the blocks this worker's documents touch ("push_pull", parameter-server
 style — less traffic when each worker sees a small part of the vocabulary).
+
+``engine="native"`` replaces that E-step by ``ops.lda_vb`` (``csrc/lda_vb.hip``): one wave
+per document with gamma in registers, no [nnz, K] matrix (the state is gamma [D, K] and the
+word-major [V, K] model), and with ``gamma_tol > 0`` every document stops on its own pass
+count, as the reference's per-document loop does, where the torch engine iterates all
+documents until the slowest one has converged. The word-topic statistics come from fp64
+atomics there (reproducible to rounding, not bitwise), and K is limited to
+``ops.lda_vb.MAX_TOPICS``. Strategies, alpha update and bound are shared by both engines.
 """
 from __future__ import annotations
 
@@ -49,6 +57,11 @@ class LDAVBConfig:
     init: str = "random"         # "uniform": the reference's start (every log beta 0.1, then
                                  # normalised: LDAMapper.java:113-130), which keeps the topics
                                  # symmetric for good
+    engine: str = "torch"        # "native": ops/lda_vb.py E-step (HIP kernels on a GPU, its torch
+                                 # reference on CPU tensors), per-document stopping, K <= 1024
+
+
+ENGINES = ("torch", "native")
 
 
 def _estep(doc, word, cnt, n_docs, log_beta, alpha, cfg):
@@ -88,12 +101,18 @@ def _elbo_terms(doc, cnt, gamma, logz, alpha, n_docs):
     fixed point it equals the reference's per-document likelihood (LDAMapper.java:239-344,
     updatePhi :679-717: lnG(sum alpha) - sum lnG(alpha) + sum lnG(gamma) - lnG(sum gamma)
     + sum_w n_w sum_k phi (log beta - log phi))."""
+    lg, dsum = _elbo_doc_part(gamma, alpha, n_docs)
+    lw = (cnt * (logz - dsum[:, 0][doc])).sum()
+    return lg, lw
+
+
+def _elbo_doc_part(gamma, alpha, n_docs):
+    """The doc part of the bound and digamma(sum_k gamma_dk) [D, 1], from gamma alone."""
     dsum = torch.digamma(gamma.sum(1, keepdim=True))
     lg = (torch.lgamma(alpha.sum()) - torch.lgamma(alpha).sum()) * n_docs
     lg = lg + ((alpha - gamma) * (torch.digamma(gamma) - dsum)).sum()
     lg = lg + (torch.lgamma(gamma).sum() - torch.lgamma(gamma.sum(1)).sum())
-    lw = (cnt * (logz - dsum[:, 0][doc])).sum()
-    return lg, lw
+    return lg, dsum
 
 
 def _alpha_newton(alpha, ss, D, iters=20):
@@ -118,6 +137,8 @@ def _alpha_newton(alpha, ss, D, iters=20):
 def train_lda_vb(comm: Communicator, doc: torch.Tensor, word: torch.Tensor, cnt: torch.Tensor, n_docs_local: int,
                  vocab: int, cfg: LDAVBConfig) -> Dict[str, object]:
     """doc/word/cnt: this worker's sparse doc-term counts (local doc ids 0..n_docs_local-1)."""
+    if cfg.engine not in ENGINES:
+        raise ValueError(f"engine must be one of {ENGINES} (got {cfg.engine!r})")
     dev = comm.device
     dt = torch.float64
     K = cfg.num_topics
@@ -133,13 +154,28 @@ def train_lda_vb(comm: Communicator, doc: torch.Tensor, word: torch.Tensor, cnt:
     hist: List[Dict[str, float]] = []
     blocks_needed = torch.unique(word // cfg.block).tolist()
     nb = math.ceil(vocab / cfg.block)
+    native = cfg.engine == "native"
+    if native:
+        from ..ops import lda_vb as E
+
+        plan = E.DocPlan.build(doc, word, n_docs_local)  # the document structure never changes
+        Nd = torch.zeros(n_docs_local, dtype=dt, device=dev).index_add_(0, doc, cnt)
+        log_beta_t = log_beta.t().contiguous()  # word-major between iterations
     for it in range(cfg.iterations):
         t0 = time.perf_counter()
-        gamma, phi, logz = _estep(doc, word, cnt, n_docs_local, log_beta, alpha, cfg)
-        S = torch.zeros((K, vocab), dtype=dt, device=dev)
-        S.index_add_(1, word, (cnt[:, None] * phi).t())
+        extra = {}
+        if native:
+            gamma, passes, doc_ll, S_t = E.estep(plan, cnt, log_beta_t, alpha, cfg.gamma_iters, cfg.gamma_tol)
+            S = S_t.t().contiguous()
+            lg, dsum = _elbo_doc_part(gamma, alpha, n_docs_local)
+            lw = doc_ll.sum() - (Nd * dsum[:, 0]).sum()
+            extra["passes_max"] = int(passes.max()) if n_docs_local else 0
+        else:
+            gamma, phi, logz = _estep(doc, word, cnt, n_docs_local, log_beta, alpha, cfg)
+            S = torch.zeros((K, vocab), dtype=dt, device=dev)
+            S.index_add_(1, word, (cnt[:, None] * phi).t())
+            lg, lw = _elbo_terms(doc, cnt, gamma, logz, alpha, n_docs_local)
         ss = (torch.digamma(gamma) - torch.digamma(gamma.sum(1, keepdim=True))).sum(0)
-        lg, lw = _elbo_terms(doc, cnt, gamma, logz, alpha, n_docs_local)
         if cfg.strategy == "push_pull" and comm.world_size > 1:
             # normaliser = global row sums (allreduce of K values), statistics by push/pull
             red = reduce_partials(comm, {"ss": ss, "ll": (lg + lw).reshape(1), "norm": S.sum(1)})
@@ -150,9 +186,11 @@ def train_lda_vb(comm: Communicator, doc: torch.Tensor, word: torch.Tensor, cnt:
             S = red["S"].to(dev)
             norm = S.sum(1)
         log_beta = (S + cfg.eta).log() - (norm + vocab * cfg.eta).log()[:, None]
+        if native:
+            log_beta_t = log_beta.t().contiguous()
         if cfg.update_alpha:
             alpha = _alpha_newton(alpha, red["ss"].to(dev), D)
-        hist.append({"iter": it + 1, "elbo": float(red["ll"][0]), "time_s": time.perf_counter() - t0})
+        hist.append({"iter": it + 1, "elbo": float(red["ll"][0]), "time_s": time.perf_counter() - t0, **extra})
     return {"log_beta": log_beta, "alpha": alpha, "gamma": gamma, "history": hist}
 
 
