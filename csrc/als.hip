@@ -311,8 +311,7 @@ __global__ __launch_bounds__(256) void als_chol_solve_kernel(const float* __rest
 #pragma unroll
   for (int j = kMaxF - 1; j >= 0; --j) {
     float t = lane > j ? a[j] * x : 0.f;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+    t = wave_sum(t);
     const float ljj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a[j]), j));
     const float yj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(b), j));
     if (lane == j) x = (yj - t) / ljj;

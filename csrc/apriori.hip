@@ -38,12 +38,6 @@ constexpr int CP = APRIORI_SLAB4 / 256;
 __device__ __forceinline__ int popc4(uint4 v) { return __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w); }
 __device__ __forceinline__ uint4 and4(uint4 a, uint4 b) { return make_uint4(a.x & b.x, a.y & b.y, a.z & b.z, a.w & b.w); }
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void apriori_pack_kernel(const int* __restrict__ tid, const int* __restrict__ item,
                                                            long npairs, int n, int n_items, long W,
                                                            unsigned* __restrict__ bits, int* __restrict__ err) {

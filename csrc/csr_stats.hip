@@ -253,18 +253,6 @@ __global__ __launch_bounds__(256) void csr_class_sums_kernel(const long* __restr
   }
 }
 
-__device__ __forceinline__ void wave_argmax_f64(double& v, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double w = __shfl_xor(v, o, 64);
-    const int wi = __shfl_xor(i, o, 64);
-    if (w > v || (w == v && wi < i)) {
-      v = w;
-      i = wi;
-    }
-  }
-}
-
 // out[r][c] = sum_p val[p] * BP[col[p]][c] + bias[c]; one wave per row, lanes over the
 // output columns in KPL register slots (64 * KPL columns per pass, as kmeans_csr.hip)
 template <int KPL>
@@ -310,7 +298,7 @@ __global__ __launch_bounds__(256) void csr_spmm_kernel(const long* __restrict__ 
       }
     }
     if (amax) {
-      wave_argmax_f64(best, besti);
+      wave_arg_xor<true>(best, besti);
       if (lane == 0) amax[r] = besti < m ? besti : 0;
     }
   }

@@ -12,9 +12,10 @@
 // matrix-vector steps: launch-bound as separate kernels, but cheap as ONE kernel whose
 // workgroups all sit on one XCD and synchronise through that XCD's L2 (two arrivals per
 // column; no L2 write-back is needed since no other XCD touches the matrix):
-//  * participants read HW_REG_XCC_ID and claim a slot only on XCD 0 (as the cooperative SMO
-//    of svm.hip); 32 workgroups x 16 waves, each workgroup a 64-row super tile of the
-//    trailing m x m block split by columns over its waves, the same tile in both phases;
+//  * participants read HW_REG_XCC_ID and claim a slot only on XCD 0 (xcc_id and grid_arrive
+//    of coop.h, which the cooperative SMO of svm.hip uses too); 32 workgroups x 16 waves,
+//    each workgroup a 64-row super tile of the trailing m x m block split by columns over
+//    its waves, the same tile in both phases;
 //  * phase 1: p = tau A v per tile row, the waves' partials summed in LDS and added into p
 //    with one fp64 atomic per row and workgroup (and p.v likewise); phase 2: the rank-2
 //    update of the tile, which also accumulates the next column's squared norm (the next
@@ -27,6 +28,7 @@
 // 16 points of its interval, so each round narrows it 17-fold (~13 rounds to machine
 // precision instead of ~53 bisections).
 #include "common.h"
+#include "coop.h"
 
 namespace {
 
@@ -37,48 +39,7 @@ constexpr int kMaxN = 4096;  // v and w staged in LDS (2 x 32 KB)
 constexpr int kWsInts = 16;
 constexpr int kU = 8;  // columns per batch of loads in flight
 
-__device__ __forceinline__ double ld_agent(const double* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int ld_agent(const int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ __forceinline__ double ld_nt(const double* p) { return __builtin_nontemporal_load(p); }
-
-// this thread's stores are complete, then thread 0 arrives and waits for all NB
-__device__ __forceinline__ bool arrive(int* cnt, int target, int* err, int* s_ok) {
-  __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    atomicAdd(cnt, 1);
-    int ok = 1;
-    long spin = 0;
-    while (ld_agent(cnt) < target) {
-      if (++spin > (1L << 22) || ld_agent(err)) {
-        ok = 0;
-        atomicExch(err, 1);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    *s_ok = ok;
-  }
-  __syncthreads();
-  return *s_ok != 0;
-}
-
-// block-wide sum, the result in every thread
-template <int T = kT>
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wave_sum_d_dpp(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < T / 64; ++w) s += red[w];
-  __syncthreads();
-  return s;
-}
 
 // A: n x n symmetric, column-major (lda), overwritten. d[n], e[n-1]: the tridiagonal.
 // wsd (doubles, zeroed): p[2][n], then pv[2], sigma[2].
@@ -95,7 +56,7 @@ __global__ __launch_bounds__(kT) void sytrd_coop_kernel(double* __restrict__ A, 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   if (tid == 0) {
     int b = -1;
-    if ((__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 0xf) == 0) b = atomicAdd(ws, 1);  // HW_REG_XCC_ID
+    if ((xcc_id() & 0xf) == 0) b = atomicAdd(ws, 1);
     s_b = b;
   }
   __syncthreads();
@@ -122,7 +83,7 @@ __global__ __launch_bounds__(kT) void sytrd_coop_kernel(double* __restrict__ A, 
     const double x = A[i];
     s0 += x * x;
   }
-  s0 = block_sum(s0, red);
+  s0 = block_sum_d<kT>(s0, red);
   for (int k = 0; k + 2 < n; ++k) {
     const int par = k & 1, off = k + 1, m = n - off;
     double* pcur = par ? pbuf1 : pbuf0;
@@ -204,7 +165,7 @@ __global__ __launch_bounds__(kT) void sytrd_coop_kernel(double* __restrict__ A, 
       }
     }
     STAMP(1)
-    if (!arrive(ws + 1, NB * ++syncs, err, &s_ok)) return;
+    if (!grid_arrive(ws + 1, NB * ++syncs, err, &s_ok)) return;
     STAMP(2)
     if (tau != 0.0) {
       const double K = -0.5 * tau * ld_agent(scal + par);
@@ -247,7 +208,7 @@ __global__ __launch_bounds__(kT) void sytrd_coop_kernel(double* __restrict__ A, 
     sp = wave_sum_d_dpp(sp);
     if (lane == 0 && sp != 0.0) atomicAdd(scal + 2 + (par ^ 1), sp);
     STAMP(4)
-    if (!arrive(ws + 1, NB * ++syncs, err, &s_ok)) return;
+    if (!grid_arrive(ws + 1, NB * ++syncs, err, &s_ok)) return;
     STAMP(5)
   }
   if (stamp)
@@ -279,7 +240,7 @@ __device__ __forceinline__ double house_lds(double* c, int L, double* red, doubl
   __syncthreads();  // c[] was written by other threads
   double s = 0.0;
   for (int i = 1 + (int)threadIdx.x; i < L; i += T) s = fma(c[i], c[i], s);
-  const double sig = block_sum<T>(s, red);  // its barriers also order the c[] writes before this read
+  const double sig = block_sum_d<T>(s, red);  // its barriers also order the c[] writes before this read
   const double alpha = c[0];
   double b = alpha, tau = 0.0, scl = 0.0;
   if (sig != 0.0) {
@@ -380,7 +341,7 @@ __global__ __launch_bounds__(kT) void sytrd_fused_kernel(double* __restrict__ A,
   const int tid = threadIdx.x;
   if (tid == 0) {
     int b = -1;
-    if ((__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 0xf) == 0) b = atomicAdd(ws, 1);  // HW_REG_XCC_ID
+    if ((xcc_id() & 0xf) == 0) b = atomicAdd(ws, 1);
     s_b = b;
   }
   __syncthreads();
@@ -412,7 +373,7 @@ __global__ __launch_bounds__(kT) void sytrd_fused_kernel(double* __restrict__ A,
     if (tid == 0) tauout[0] = tn;
   }
   fused_pass<KU>(A, lda, 1, n - 1, b, NB, false, nullptr, nullptr, tn, sn, wsd, spart);
-  if (!arrive(ws + 1, NB * ++syncs, err, &s_ok)) return;
+  if (!grid_arrive(ws + 1, NB * ++syncs, err, &s_ok)) return;
   // diagnostic (stamps != nullptr): workgroup 0 / thread 0 sums the cycles of each phase
   const bool stamp = stamps != nullptr && b == 0 && tid == 0;
   long long ph[4] = {0, 0, 0, 0}, t_last = stamp ? (long long)__builtin_amdgcn_s_memtime() : 0;
@@ -448,7 +409,7 @@ __global__ __launch_bounds__(kT) void sytrd_fused_kernel(double* __restrict__ A,
       const int i = tid + q * kT;
       if (i < m) s = fma(pr[q], sv[i], s);
     }
-    const double K = -0.5 * tk * block_sum(s, red);
+    const double K = -0.5 * tk * block_sum_d<kT>(s, red);
 #pragma unroll
     for (int q = 0; q < R; ++q) {
       const int i = tid + q * kT;
@@ -489,7 +450,7 @@ __global__ __launch_bounds__(kT) void sytrd_fused_kernel(double* __restrict__ A,
     // trailing block of the next step: update by (v_k, w_k) and p_{k+1} in one pass
     fused_pass<KU>(A, lda, off + 1, m - 1, b, NB, tk != 0.0, sv + 1, sw + 1, tn, sn, pn, spart);
     mark(2);
-    if (!arrive(ws + 1, NB * ++syncs, err, &s_ok)) return;
+    if (!grid_arrive(ws + 1, NB * ++syncs, err, &s_ok)) return;
     mark(3);
   }
   if (stamp)
@@ -530,11 +491,9 @@ __global__ __launch_bounds__(256) void tridiag_multisect_kernel(const double* __
     emax = fmax(emax, er);
   }
   // Gershgorin bounds and the pivot floor (block reductions through LDS)
-  for (int o = 32; o > 0; o >>= 1) {
-    glo = fmin(glo, __shfl_xor(glo, o, 64));
-    ghi = fmax(ghi, __shfl_xor(ghi, o, 64));
-    emax = fmax(emax, __shfl_xor(emax, o, 64));
-  }
+  glo = wave_min_d(glo);
+  ghi = wave_max_d(ghi);
+  emax = wave_max_d(emax);
   if ((tid & 63) == 0) {
     red[tid >> 6] = glo;
     red[4 + (tid >> 6)] = ghi;

@@ -113,17 +113,6 @@ __device__ __forceinline__ int butterfly_slot(int lane) {
   return ((lane >> 5) & 1) * 8 + ((lane >> 4) & 1) * 4 + ((lane >> 3) & 1) * 2 + ((lane >> 2) & 1);
 }
 
-// 1 / x by v_rcp_f64 and two Newton steps (the IEEE divide is a ~10-instruction dependent chain)
-__device__ __forceinline__ double rcp_d(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(r, fma(-x, r, 1.0), r);
-  return fma(r, fma(-x, r, 1.0), r);
-}
-
-// workgroup barrier for LDS traffic only: __syncthreads() also drains vmcnt, i.e. waits for
-// the granule stores and for the column prefetch issued a phase earlier
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 __device__ __forceinline__ bool spin_fail(long& spins, int* err) {
   if (++spins > kSpinLimit) {
     __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -271,7 +260,7 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       sP[par][wv][lane] = 0.0;
     }
     mark(0);
-    lds_barrier();
+    lds_sync();  // not __syncthreads(): the granule stores and the column prefetch stay in flight
     double tot = 0.0;
     if (lane < kSlots) tot = (sP[par][0][lane] + sP[par][1][lane]) + (sP[par][2][lane] + sP[par][3][lane]);
     const double sigma = readlane_d(tot, 0);
@@ -279,8 +268,8 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     double beta = alpha, tau = 0.0, scl = 0.0;
     if (sigma != 0.0) {
       beta = -copysign(sqrt(alpha * alpha + sigma), alpha);
-      tau = (beta - alpha) * rcp_d(beta);
-      scl = rcp_d(alpha - beta);
+      tau = (beta - alpha) * rcp_newton_d(beta);
+      scl = rcp_newton_d(alpha - beta);
     }
     const double gam = sigma != 0.0 ? -beta * scl : 1.0;  // v = scl x' + gam e_{k+1}
     double v[kIPT];
@@ -420,7 +409,7 @@ __global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     tmark(k, 2);
     // (measured: letting every wave poll the partial sums itself to drop this barrier on
     // non-panel columns cost more polling traffic than the barrier: 6.8 -> 7.8 ms)
-    lds_barrier();
+    lds_sync();
     const double c = 0.5 * tau * sB2[0];
 #pragma unroll
     for (int m = 0; m < kIPT; ++m) Ww[j][m] = t0 + m >= k1 ? fma(-c, v[m], p[m]) : 0.0;

@@ -83,12 +83,6 @@ __device__ __forceinline__ uint32_t hash4(uint32_t a, uint32_t b, uint32_t c, ui
   return fmix(hash3(a, b, c) ^ (d * 0x27D4EB2Fu));
 }
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // node of chunk `b`: the j with chunk_off[j] <= b < chunk_off[j + 1]; -1 past the end
 __device__ __forceinline__ int chunk_node(const int* __restrict__ chunk_off, int M, int b) {
   if (b >= chunk_off[M]) return -1;
@@ -323,15 +317,7 @@ __global__ __launch_bounds__(64) void split_feature_kernel(const T* __restrict__
       bb = b;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double og = __shfl_xor(best, o, 64);
-    const int ob = __shfl_xor(bb, o, 64);
-    if (og > best || (og == best && ob < bb)) {
-      best = og;
-      bb = ob;
-    }
-  }
+  wave_arg_xor<true>(best, bb);
   if (lane == 0) {
     cand_gain[jf] = best;
     cand_bin[jf] = bb == 0x7fffffff ? 0 : bb;
@@ -356,15 +342,7 @@ __global__ __launch_bounds__(64) void split_node_kernel(const T* __restrict__ H,
       bf = f;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double og = __shfl_xor(best, o, 64);
-    const int of = __shfl_xor(bf, o, 64);
-    if (og > best || (og == best && of < bf)) {
-      best = og;
-      bf = of;
-    }
-  }
+  wave_arg_xor<true>(best, bf);
   if (bf < 0 || bf >= d) bf = 0;  // only if every gain is NaN (overflowed statistics)
   int bin = cand_bin[j * d + bf];
   if (bin < 0 || bin >= B) bin = 0;

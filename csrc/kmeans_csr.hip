@@ -21,25 +21,6 @@
 
 namespace {
 
-__device__ __forceinline__ void wave_argmin_f64(double& v, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double w = __shfl_xor(v, o, 64);
-    const int wi = __shfl_xor(i, o, 64);
-    if (w < v || (w == v && wi < i)) {
-      v = w;
-      i = wi;
-    }
-  }
-}
-
-__device__ __forceinline__ double readlane_f64(double x, int t) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, t);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), t);
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-
 template <int KPL>
 __global__ __launch_bounds__(256) void kmeans_csr_assign_kernel(const long* __restrict__ rowptr,
                                                                 const int* __restrict__ col,
@@ -65,7 +46,7 @@ __global__ __launch_bounds__(256) void kmeans_csr_assign_kernel(const long* __re
         const double vl = lane < cnt ? val[p0 + lane] : 0.0;
         for (int t = 0; t < cnt; ++t) {
           const int j = __builtin_amdgcn_readlane(jl, t);
-          const double v = readlane_f64(vl, t);
+          const double v = readlane_d(vl, t);
           const double* ct = CT + (long)j * Kp + c0 + lane;
 #pragma unroll
           for (int i = 0; i < KPL; ++i)
@@ -84,7 +65,7 @@ __global__ __launch_bounds__(256) void kmeans_csr_assign_kernel(const long* __re
         }
       }
     }
-    wave_argmin_f64(best, besti);
+    wave_arg_xor<false>(best, besti);
     if (lane == 0) {
       labels[r] = besti;
       const double m = best + xn[r];

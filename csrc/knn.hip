@@ -44,21 +44,6 @@ __device__ __forceinline__ void list_insert(float (&dl)[KK], int (&il)[KK], floa
   }
 }
 
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long w = __shfl_xor(v, o, 64);
-    v = w < v ? w : v;
-  }
-  return v;
-}
-
-__device__ __forceinline__ float wave_min_f32(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 template <int KK>
 __global__ __launch_bounds__(256) void knn_select_kernel(const float* __restrict__ S, long lds, int M, int N,
                                                          const float* __restrict__ qn, const float* __restrict__ tn,
@@ -96,7 +81,7 @@ __global__ __launch_bounds__(256) void knn_select_kernel(const float* __restrict
   int base = 0;
   for (int it = 0; base + 255 < N; base += 256, ++it) {
     const int j = base + lane;
-    if ((it & 3) == 3) thr = fminf(thr, wave_min_f32(dl[KK - 1]));
+    if ((it & 3) == 3) thr = fminf(thr, wave_min_f(dl[KK - 1]));
     const float s0 = row[j], s1 = row[j + 64], s2 = row[j + 128], s3 = row[j + 192];
     const float t0 = tn[j], t1 = tn[j + 64], t2 = tn[j + 128], t3 = tn[j + 192];
     const float d0 = fmaxf(fmaf(-2.f, s0, qq + t0), 0.f), d1 = fmaxf(fmaf(-2.f, s1, qq + t1), 0.f);

@@ -28,6 +28,7 @@
 //  * the flat kernel (mf_sgd_kernel) keeps the original one-stream-per-chunk launch for
 //    comparison and for unblocked rating sets.
 #include "common.h"
+#include "coop.h"
 
 #include <climits>
 #include <type_traits>
@@ -117,22 +118,6 @@ __device__ __forceinline__ void load_w(const float* __restrict__ p, float (&x)[E
     load_row_l2<EPL>(p, x);
   else
     load_row<EPL>(p, x);
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-
-// Sum over the 16 lanes of a DPP row (= one update stream), result in every lane: row
-// rotations by 8 and 4, then the two quad permutations. Four dependent VALU ops with DPP
-// operands instead of four ds_bpermute round trips through the LDS crossbar.
-__device__ __forceinline__ float sub16_sum(float v) {
-  v += dpp<0x128>(v);  // row_ror:8
-  v += dpp<0x124>(v);  // row_ror:4
-  v += dpp<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += dpp<0xB1>(v);   // quad_perm [1,0,3,2]
-  return v;
 }
 
 __device__ __forceinline__ int shfl16(int v, int src) { return __shfl(v, src, 16); }
@@ -457,17 +442,13 @@ __device__ __forceinline__ unsigned tag_once(unsigned long long* p, unsigned lon
   return (unsigned)(cur & 0xff);
 }
 
-__device__ __forceinline__ int hw_xcc_id() {
-  return __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 0xf;  // HW_REG_XCC_ID
-}
-
 // Called by thread 0 at the END of a block (at the start, every block's first barrier waited
 // on these device-scope atomics, which all blocks of a residue aim at one word: 2.5 % of an
 // epoch). Only residue -> XCC is checked: it is what coherence needs (all of a residue's
 // blocks in one L2); two residues sharing an XCD touch disjoint W / H blocks.
 __device__ __forceinline__ void placement_check(unsigned long long* chk, unsigned long long gen, int x) {
   if (chk == nullptr || threadIdx.x != 0) return;
-  const int hw = hw_xcc_id();
+  const int hw = xcc_id() & 0xf;
   if (tag_once(chk + x, gen, (unsigned)hw + 1) != (unsigned)hw + 1)
     __hip_atomic_store(chk + kChkErr, 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -576,7 +557,7 @@ __global__ __launch_bounds__(256) void mf_sgd_xcd_placed_kernel(const int* __res
   __shared__ int sR[16 * CH], sC[16 * CH];
   __shared__ float sV[16 * CH];
   __shared__ int s_round, s_last;
-  const int x = hw_xcc_id() & (XCDS - 1);
+  const int x = xcc_id() & 0xf & (XCDS - 1);
   Cell c = cell_of(off, win, x, step);
   const long rounds = (c.n + 16 * CH - 1) / (16 * CH);
   for (;;) {
@@ -674,7 +655,7 @@ __global__ __launch_bounds__(256) void mf_sgd_xcd_flow_kernel(const int* __restr
   // records its XCC id; a block of x on another XCC, or two residues on one XCC, raise the
   // error word (2) and the host refuses the pass (ops.mf.check_flow_errors)
   if (threadIdx.x == 0) {
-    const int hw = hw_xcc_id() + 1;
+    const int hw = (xcc_id() & 0xf) + 1;
     const int prev = cas_zero(xccmap + x, hw);
     if (prev != 0 && prev != hw) __hip_atomic_store(err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int bit = 1 << (hw - 1);
@@ -867,13 +848,6 @@ int launch_sgd_xcd(XcdArgs a, int steps, dim3 grid, int variant, unsigned long l
 // streams of the narrow kernels (R / 16 floats per lane); the dot product is a full-wave
 // reduction. The next rating's H row is prefetched before this rating's H store (vmcnt
 // retires in order: the wait for the prefetch never covers the store).
-__device__ __forceinline__ float wave_sum_f(float v) {
-  v = sub16_sum(v);
-  v += __shfl_xor(v, 16);
-  v += __shfl_xor(v, 32);
-  return v;
-}
-
 template <int Q, bool NT>
 __device__ __forceinline__ void load_wide(const float* __restrict__ p, int lane, int R, floatx4 (&x)[Q]) {
 #pragma unroll
@@ -929,7 +903,7 @@ __device__ __forceinline__ void sgd_stream_wide(const int* __restrict__ rows, co
       d = fmaf(w[q][2], h[q][2], d);
       d = fmaf(w[q][3], h[q][3], d);
     }
-    const float ge = -lr * (wave_sum_f(d) - v);
+    const float ge = -lr * (wave_sum_rows(d) - v);
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
       const floatx4 wk = w[q], hk = h[q];
@@ -1008,7 +982,7 @@ __global__ __launch_bounds__(256) void mf_rmse_wide_kernel(const int* __restrict
 #pragma unroll
     for (int q = 0; q < Q; ++q)
       d += w[q][0] * h[q][0] + w[q][1] * h[q][1] + w[q][2] * h[q][2] + w[q][3] * h[q][3];
-    const float e = vals[i] - wave_sum_f(d);
+    const float e = vals[i] - wave_sum_rows(d);
     acc += (double)e * e;
   }
   double s = lane == 0 ? acc : 0.0;

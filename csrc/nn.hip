@@ -57,8 +57,7 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
     const float* zr = z + (long)row * C;
     float m = -3.4e38f;
     for (int c = lane; c < C; c += 64) m = fmaxf(m, zr[c]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = wave_max_f(m);
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s += __expf(zr[c] - m);
     s = wave_sum(s);

@@ -19,12 +19,6 @@ namespace {
 
 constexpr int kWaves = 4;  // waves (rows) per 256-thread workgroup
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(kWaves * 64) void slab_nnz_kernel(const int* __restrict__ slab, int rows, int cols,
                                                               long ld, int* __restrict__ nnz) {
   const int row = blockIdx.x * kWaves + (threadIdx.x >> 6);

@@ -27,108 +27,16 @@
 // gradient in global memory and one element's gathers in flight at a time, spent ~44 us per
 // step at n = 20k in serialized memory round trips.
 #include "common.h"
+#include "coop.h"
 
 #include <type_traits>
 
 namespace {
 
 
-struct ArgMax {
-  double v;
-  int i;
-};
-
-// better(a, b): a larger value, or an equal value at a lower index
-__device__ __forceinline__ bool better_max(double va, int ia, double vb, int ib) {
-  return va > vb || (va == vb && ia < ib);
-}
-__device__ __forceinline__ bool better_min(double va, int ia, double vb, int ib) {
-  return va < vb || (va == vb && ia < ib);
-}
-
-// Wave reductions without the LDS crossbar: DPP inside each 16-lane row (row_ror 8, 4, then
-// the two quad permutations: every lane ends with its row's result), then the four row
-// results through v_readlane. (__shfl_xor compiles to ds_bpermute: six dependent LDS round
-// trips per reduction, ~0.4 us, and a step runs six of them.)
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int x) {
-  return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, false);
-}
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double x) {
-  const long long b = __double_as_longlong(x);
-  const int lo = dpp_i<CTRL>((int)(b & 0xffffffffll)), hi = dpp_i<CTRL>((int)(b >> 32));
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-__device__ __forceinline__ double readlane_d(double x, int l) {
-  const long long b = __double_as_longlong(x);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), l), hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-
-template <bool MAX>
-__device__ __forceinline__ void arg_take(double& v, int& i, double ov, int oi) {
-  if (MAX ? better_max(ov, oi, v, i) : better_min(ov, oi, v, i)) {
-    v = ov;
-    i = oi;
-  }
-}
-
-template <bool MAX, int CTRL>
-__device__ __forceinline__ void arg_dpp(double& v, int& i) {
-  arg_take<MAX>(v, i, dpp_d<CTRL>(v), dpp_i<CTRL>(i));
-}
-
-template <bool MAX>
-__device__ __forceinline__ void row_arg(double& v, int& i) {
-  arg_dpp<MAX, 0x128>(v, i);  // row_ror:8
-  arg_dpp<MAX, 0x124>(v, i);  // row_ror:4
-  arg_dpp<MAX, 0x4E>(v, i);   // quad_perm [2,3,0,1]
-  arg_dpp<MAX, 0xB1>(v, i);   // quad_perm [1,0,3,2]
-}
-
-// (value, index) arg-max / arg-min over the wave, ties to the lower index; uniform result
-template <bool MAX>
-__device__ __forceinline__ void wave_arg(double& v, int& i) {
-  row_arg<MAX>(v, i);
-  double r = readlane_d(v, 0);
-  int ri = __builtin_amdgcn_readlane(i, 0);
-#pragma unroll
-  for (int q = 16; q < 64; q += 16) arg_take<MAX>(r, ri, readlane_d(v, q), __builtin_amdgcn_readlane(i, q));
-  v = r;
-  i = ri;
-}
-
-__device__ __forceinline__ double row_min(double v) {
-  v = fmin(v, dpp_d<0x128>(v));
-  v = fmin(v, dpp_d<0x124>(v));
-  v = fmin(v, dpp_d<0x4E>(v));
-  return fmin(v, dpp_d<0xB1>(v));
-}
-
-__device__ __forceinline__ double wave_min(double v) {
-  v = row_min(v);
-  return fmin(fmin(readlane_d(v, 0), readlane_d(v, 16)), fmin(readlane_d(v, 32), readlane_d(v, 48)));
-}
-
-// block arg-reduction: each wave's result through LDS, then EVERY wave reduces the <= 16
-// partials itself (one row of lanes), so no second barrier; the arrays are not written
-// again before the step's closing barrier
-template <bool MAX, int T>
-__device__ __forceinline__ void block_arg(double& v, int& i, double* sv, int* si, int lane, int wv) {
-  wave_arg<MAX>(v, i);
-  if (lane == 0) {
-    sv[wv] = v;
-    si[wv] = i;
-  }
-  __syncthreads();
-  const double id = MAX ? -__builtin_inf() : __builtin_inf();
-  v = lane < T / 64 ? sv[lane] : id;
-  i = lane < T / 64 ? si[lane] : 0x7fffffff;
-  row_arg<MAX>(v, i);
-  v = readlane_d(v, 0);
-  i = __builtin_amdgcn_readlane(i, 0);
-}
+// Arg-reductions (ties to the lower index), the DPP wave / block reductions: wave.h.
+// (__shfl_xor compiles to ds_bpermute: six dependent LDS round trips per reduction,
+// ~0.4 us, and a step runs six of them, so every reduction of a step is a DPP form.)
 
 // Thread t owns elements t + T k (k < EPT): gradient G and three box-state bit masks in
 // registers (IDENT: the machine is the whole matrix, column = element; else the columns in
@@ -211,18 +119,18 @@ __global__ __launch_bounds__(T) void smo_kernel(const double* __restrict__ Kfull
         const double mg = yp ? -G[k] : G[k];
         const bool up = (yp && lc) || (!yp && g0);
         const bool low = (yp && g0) || (!yp && lc);
-        if (up && better_max(mg, t, bv, bi)) {
+        if (up && arg_better<true>(mg, t, bv, bi)) {
           bv = mg;
           bi = t;
         }
         if (low) lo = fmin(lo, mg);
       }
     }
-    lo = wave_min(lo);
+    lo = wave_min_d_dpp(lo);
     if (lane == 0) s_w1[wv] = lo;
     block_arg<true, T>(bv, bi, s_v1, s_i1, lane, wv);
     lo = lane < T / 64 ? s_w1[lane] : POS;
-    const double mval = bv, Mv = readlane_d(row_min(lo), 0);
+    const double mval = bv, Mv = readlane_d(row_min_d(lo), 0);
     const int i = bi;
     if (!(mval - Mv >= eps) || i >= n) break;  // converged (or no candidate: NaN-safe)
     // the owner of i fetches a_i now; it lands while the j phase runs (an element's alpha
@@ -263,7 +171,7 @@ __global__ __launch_bounds__(T) void smo_kernel(const double* __restrict__ Kfull
           double at = __dsub_rn(__dadd_rn(kii, kdu), __dmul_rn(2.0, kit[u]));
           if (!(at > 0)) at = tau;
           const double sc = -__ddiv_rn(__dmul_rn(bt, bt), at);
-          if (better_min(sc, t, sv, sj)) {
+          if (arg_better<false>(sc, t, sv, sj)) {
             sv = sc;
             sj = t;
             sat = at;
@@ -416,35 +324,6 @@ constexpr int kCoopMaxNB = 16;
 constexpr int kCoopXcdInts = 16 + 10 * 16 * 2 + 2 * 16;
 constexpr int kCoopWsInts = 8 * kCoopXcdInts;
 
-__device__ __forceinline__ double ld_agent(const double* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int ld_agent(const int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// every thread's slot stores are complete, then thread 0 arrives and waits for all NB
-__device__ __forceinline__ bool coop_arrive(int* cnt, int target, int* err, int* s_ok) {
-  __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    atomicAdd(cnt, 1);
-    int ok = 1;
-    long spin = 0;
-    while (ld_agent(cnt) < target) {
-      if (++spin > (1L << 22) || ld_agent(err)) {
-        ok = 0;
-        atomicExch(err, 1);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    *s_ok = ok;
-  }
-  __syncthreads();
-  return *s_ok != 0;
-}
-
 template <int EPT, bool IDENT>
 __global__ __launch_bounds__(kCoopT) void smo_coop_kernel(const double* __restrict__ Kfull, long ldk,
                                                           const int* __restrict__ ids_all,
@@ -459,7 +338,7 @@ __global__ __launch_bounds__(kCoopT) void smo_coop_kernel(const double* __restri
   __shared__ int s_i1[16], s_i2[16];
   __shared__ int s_b, s_ok;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int x = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7;  // HW_REG_XCC_ID
+  const int x = xcc_id() & 7;
   if (x >= nm) return;  // no machine for this XCD
   int* ws = ws_all + x * kCoopXcdInts;
   if (tid == 0) s_b = atomicAdd(ws, 1);
@@ -512,18 +391,18 @@ __global__ __launch_bounds__(kCoopT) void smo_coop_kernel(const double* __restri
       if (t < n) {
         const bool yp = (ypos >> k) & 1, lc = (ltC >> k) & 1, z0 = (gt0 >> k) & 1;
         const double mg = yp ? -G[k] : G[k];
-        if (((yp && lc) || (!yp && z0)) && better_max(mg, t, bv, bi)) {
+        if (((yp && lc) || (!yp && z0)) && arg_better<true>(mg, t, bv, bi)) {
           bv = mg;
           bi = t;
         }
         if ((yp && z0) || (!yp && lc)) lo = fmin(lo, mg);
       }
     }
-    lo = wave_min(lo);
+    lo = wave_min_d_dpp(lo);
     if (lane == 0) s_w1[wv] = lo;
     block_arg<true, T>(bv, bi, s_v1, s_i1, lane, wv);
     lo = lane < T / 64 ? s_w1[lane] : POS;
-    lo = readlane_d(row_min(lo), 0);
+    lo = readlane_d(row_min_d(lo), 0);
     if (tid == 0) {
       A_v[b] = bv;
       A_lo[b] = lo;
@@ -535,7 +414,7 @@ __global__ __launch_bounds__(kCoopT) void smo_coop_kernel(const double* __restri
       A_kd[b] = KD[k];
       A_y[b] = ((ypos >> k) & 1) ? 1.0 : -1.0;
     }
-    if (!coop_arrive(ws + 1, NB * ++na, err, &s_ok)) return;
+    if (!grid_arrive(ws + 1, NB * ++na, err, &s_ok)) return;
     double mval, Mv, ai, kii, yi;
     int i;
     {
@@ -552,7 +431,7 @@ __global__ __launch_bounds__(kCoopT) void smo_coop_kernel(const double* __restri
       row_arg<true>(v, ii);
       mval = readlane_d(v, 0);
       i = __builtin_amdgcn_readlane(ii, 0);
-      Mv = readlane_d(row_min(w), 0);
+      Mv = readlane_d(row_min_d(w), 0);
       const int wb = i < n ? (i % S) / T : 0;
       ai = readlane_d(fa, wb);
       kii = readlane_d(fk, wb);
@@ -579,7 +458,7 @@ __global__ __launch_bounds__(kCoopT) void smo_coop_kernel(const double* __restri
         double at = __dsub_rn(__dadd_rn(kii, KD[k]), __dmul_rn(2.0, KI[k]));
         if (!(at > 0)) at = tau;
         const double sc = -__ddiv_rn(__dmul_rn(bt, bt), at);
-        if (better_min(sc, t, sv, sj)) {
+        if (arg_better<false>(sc, t, sv, sj)) {
           sv = sc;
           sj = t;
           sat = at;
@@ -601,7 +480,7 @@ __global__ __launch_bounds__(kCoopT) void smo_coop_kernel(const double* __restri
       B_a[b] = A[k];
       B_y[b] = ((ypos >> k) & 1) ? 1.0 : -1.0;
     }
-    if (!coop_arrive(ws + 2, NB * ++nb, err, &s_ok)) return;
+    if (!grid_arrive(ws + 2, NB * ++nb, err, &s_ok)) return;
     double btj, atj, aj, yj;
     int j;
     {
@@ -673,7 +552,7 @@ __global__ __launch_bounds__(kCoopT) void smo_coop_kernel(const double* __restri
   if (b == 0 && tid == 0) iters[m] = it;
   // the last step may have ended after the i sync: every participant has read those slots
   // before the next machine rewrites them
-  if (!coop_arrive(ws + 2, NB * ++nb, err, &s_ok)) return;
+  if (!grid_arrive(ws + 2, NB * ++nb, err, &s_ok)) return;
   }
 #undef COLC
 }

@@ -34,45 +34,6 @@ namespace {
 constexpr int kMaxN = 4096;
 constexpr double kEps = 2.220446049250313e-16;
 
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_prod_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v *= __shfl_xor(v, o, 64);
-  return v;
-}
-
-// block reductions (1024 threads), result in every thread
-__device__ __forceinline__ double block_sum_1k(double v, double* red) {
-  v = wave_sum_d_dpp(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];
-  return s;
-}
-__device__ __forceinline__ double block_max_1k(double v, double* red) {
-  v = wave_max_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s = fmax(s, red[w]);
-  return s;
-}
-
-// workgroup barrier for LDS traffic only (__syncthreads() also drains outstanding global loads)
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// LDS ordering within one wave (its lanes run in lockstep: no barrier)
-__device__ __forceinline__ void lds_sync_wave() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // merge holding position c (merges sorted by lo, nm of them)
 __device__ __forceinline__ int find_merge(const int* __restrict__ mg, int nm, int c) {
   int a = 0, b = nm - 1;
@@ -87,18 +48,14 @@ __device__ __forceinline__ int find_merge(const int* __restrict__ mg, int nm, in
 // diagnostic: thread 0 of the last launch's first merge records s_memtime at its phase ends
 // (harp_dc_prep_stamps)
 __device__ long long g_prep_t[10];
-#define PREP_MARK(i) \
+#define DC_MARK(stamps, i) \
   do {                                                                                   \
-    if (blockIdx.x == 0 && threadIdx.x == 0) g_prep_t[i] = (long long)__builtin_amdgcn_s_memtime(); \
+    if (blockIdx.x == 0 && threadIdx.x == 0) stamps[i] = (long long)__builtin_amdgcn_s_memtime(); \
   } while (0)
 
 // phase stamps of block 0 of the last dc_wave_merge_kernel launch (harp_dc_wave_stamps)
 __device__ long long g_wave_t[8];
 __device__ int g_wave_it;
-#define WAVE_MARK(i) \
-  do {                                                                                   \
-    if (blockIdx.x == 0 && threadIdx.x == 0) g_wave_t[i] = (long long)__builtin_amdgcn_s_memtime(); \
-  } while (0)
 
 struct DcWs {
   double *dd, *zz, *tau, *zh, *rho, *U, *rotc, *rots, *sortbuf;
@@ -128,7 +85,7 @@ __global__ __launch_bounds__(1024) void dc_prep_kernel(double* __restrict__ Q, l
   __shared__ int s_k, s_nd, s_nrot, s_serial;
   __shared__ unsigned long long passm[kMaxN / 64];
   const int tid = threadIdx.x, T = blockDim.x;
-  PREP_MARK(0);
+  DC_MARK(g_prep_t, 0);
   const double beta = e[mid - 1];
   const double sgn = beta < 0.0 ? -1.0 : 1.0;
   // raw values: left block's last row, right block's first row (sign of beta folded in)
@@ -137,7 +94,7 @@ __global__ __launch_bounds__(1024) void dc_prep_kernel(double* __restrict__ Q, l
     sz[j] = j < s1 ? Q[(long)(lo + j) * ldq + (mid - 1)] : sgn * Q[(long)(lo + j) * ldq + mid];
   }
   __syncthreads();
-  PREP_MARK(1);
+  DC_MARK(g_prep_t, 1);
   // sort (value, index) pairs ascending, ties by index. Each half is the output of a child
   // merge: its kept roots ascending, then its deflated values ascending -- at most one descent
   // per half, so the input is at most four sorted runs and every element's sorted position is
@@ -224,7 +181,7 @@ __global__ __launch_bounds__(1024) void dc_prep_kernel(double* __restrict__ Q, l
       }
     }
   }
-  PREP_MARK(2);
+  DC_MARK(g_prep_t, 2);
   // z in the sorted order, through keep / defl (free until the deflation) as 32-bit halves
   for (int j = tid; j < s; j += T) {
     const double z = sz[src[j]];
@@ -237,14 +194,14 @@ __global__ __launch_bounds__(1024) void dc_prep_kernel(double* __restrict__ Q, l
     hm[j] = src[j] < s1 ? 1 : 2;
   }
   __syncthreads();
-  PREP_MARK(3);
+  DC_MARK(g_prep_t, 3);
   double nz2 = 0.0, dmax = 0.0;
   for (int j = tid; j < s; j += T) {
     nz2 = fma(sz[j], sz[j], nz2);
     dmax = fmax(dmax, fabs(sd[j]));
   }
-  nz2 = block_sum_1k(nz2, red);
-  dmax = block_max_1k(dmax, red);
+  nz2 = block_sum_d_pre(nz2, red);
+  dmax = block_max_d_pre(dmax, red);
   const double rho = fabs(beta) * nz2;
   const double inz = nz2 > 0.0 ? 1.0 / sqrt(nz2) : 0.0;
   double zmax = 0.0;
@@ -252,8 +209,8 @@ __global__ __launch_bounds__(1024) void dc_prep_kernel(double* __restrict__ Q, l
     sz[j] *= inz;
     zmax = fmax(zmax, fabs(sz[j]));
   }
-  zmax = block_max_1k(zmax, red);
-  PREP_MARK(4);
+  zmax = block_max_d_pre(zmax, red);
+  DC_MARK(g_prep_t, 4);
   const double tol = 8.0 * kEps * fmax(dmax, rho * zmax);
   // parallel pre-check: does any pair of consecutive small-z survivors pass the rotation
   // test? If not, the walk below reduces to a compaction (done in parallel)
@@ -271,7 +228,7 @@ __global__ __launch_bounds__(1024) void dc_prep_kernel(double* __restrict__ Q, l
     }
   }
   __syncthreads();
-  PREP_MARK(5);
+  DC_MARK(g_prep_t, 5);
   if (rho == 0.0) {  // decoupled halves: everything deflates, in sorted order
     for (int j = tid; j < s; j += T) defl[j] = j;
     if (tid == 0) {
@@ -398,7 +355,7 @@ __global__ __launch_bounds__(1024) void dc_prep_kernel(double* __restrict__ Q, l
   }
   __threadfence_block();
   __syncthreads();
-  PREP_MARK(6);
+  DC_MARK(g_prep_t, 6);
   const int k = s_k, nd = s_nd, nrot = s_nrot;
   // deflation rotations on Q's columns, in order (each row independent). A column takes part
   // in at most two rotations, consecutive ones (y of step q = x of step q + 1, a chain), so
@@ -435,7 +392,7 @@ __global__ __launch_bounds__(1024) void dc_prep_kernel(double* __restrict__ Q, l
       }
     }
   }
-  PREP_MARK(7);
+  DC_MARK(g_prep_t, 7);
   for (int i = tid; i < k; i += T) {
     const int j = keep[i];
     w.dd[lo + i] = sd[j];
@@ -464,7 +421,7 @@ __global__ __launch_bounds__(1024) void dc_prep_kernel(double* __restrict__ Q, l
       w.kr[lo] = nr2;
     }
   }
-  PREP_MARK(8);
+  DC_MARK(g_prep_t, 8);
   if (tid == 0) {
     w.kcnt[lo] = k;
     w.rho[lo] = rho;
@@ -477,12 +434,6 @@ __global__ __launch_bounds__(1024) void dc_prep_kernel(double* __restrict__ Q, l
 // (the iterations re-read them from L2 otherwise) and forms 1 / (d_j - d_o - tau) with
 // v_rcp_f64 + two Newton steps instead of the IEEE divide chain.
 constexpr int kSecR = 16;
-__device__ __forceinline__ double rcp_nr(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(r, fma(-x, r, 1.0), r);
-  return fma(r, fma(-x, r, 1.0), r);
-}
-
 // Initial tau of root i < k - 1 (LAPACK dlaed4's two-pole start): f0 is the secular function
 // at the gap's midpoint, c = f0 without the two nearest poles' terms, and the root of
 // c + z_i^2 / (d_i - l) + z_{i+1}^2 / (d_{i+1} - l) in the half f0's sign selects (origin d_i:
@@ -570,7 +521,7 @@ __device__ __forceinline__ void secular_solve(int i, int k, int lane, double rho
       for (int q = 0; q < kSecR; ++q) {
         const int j = lane + 64 * q;
         if (j < k) {
-          const double r = rcp_nr(dr[q] - tau);
+          const double r = rcp_newton_d(dr[q] - tau);
           const double t = z2r[q] * r;
           if (j <= i) {
             psi += t;
@@ -926,7 +877,7 @@ __device__ int secular_quad(int i, int part, int k, double rho, const double* dd
 #pragma unroll
     for (int q = 0; q < NT; ++q) {  // branch-free: the split j <= i as selects
       const bool left = part + 4 * q <= i;
-      const double r = rcp_nr(dr[q] - tau);
+      const double r = rcp_newton_d(dr[q] - tau);
       const double t = z2r[q] * r;
       const double tl = left ? t : 0.0, tg = left ? 0.0 : t;
       psi += tl;
@@ -1029,7 +980,7 @@ __global__ __launch_bounds__(256) void dc_wave_merge_kernel(double* __restrict__
   const unsigned long long below = (1ull << lane) - 1ull;
   const double beta = e[mid - 1];
   const double sgn = beta < 0.0 ? -1.0 : 1.0;
-  WAVE_MARK(0);
+  DC_MARK(g_wave_t, 0);
   {  // stage the block: up to 16 loads in flight per thread (one round trip for s <= 64)
     const int tot = s * s;
     for (int q0 = 0; q0 < tot; q0 += 256 * 16) {
@@ -1047,7 +998,7 @@ __global__ __launch_bounds__(256) void dc_wave_merge_kernel(double* __restrict__
     }
   }
   __syncthreads();
-  WAVE_MARK(1);
+  DC_MARK(g_wave_t, 1);
   if (wv == 0) {  // sort, deflation, rotations: wave 0, lane = sorted position
     // z: the left block's last row, the right block's first row (sign of beta folded in)
     double zr = 0.0, key = __builtin_inf();
@@ -1174,11 +1125,11 @@ __global__ __launch_bounds__(256) void dc_wave_merge_kernel(double* __restrict__
     }
   }
   __syncthreads();
-  WAVE_MARK(2);
+  DC_MARK(g_wave_t, 2);
   const int k = s_k;
   const double rho = s_rho;
   const int i4 = tid >> 2, part = tid & 3;
-  WAVE_MARK(3);
+  DC_MARK(g_wave_t, 3);
   int its = 0;
   if (i4 < k) {  // secular root i4 by a quad
     int o;
@@ -1195,7 +1146,7 @@ __global__ __launch_bounds__(256) void dc_wave_merge_kernel(double* __restrict__
     if (lane == 0) g_wave_it = mx;
   }
   __syncthreads();
-  WAVE_MARK(4);
+  DC_MARK(g_wave_t, 4);
   if (i4 < k) {  // Loewner z-hat of position i4 by a quad
     const double dl = dd[i4];
     double pr = 1.0;
@@ -1211,7 +1162,7 @@ __global__ __launch_bounds__(256) void dc_wave_merge_kernel(double* __restrict__
     if (part == 0) zh[i4] = copysign(sqrt(fmax(pr, 0.0)), zz[i4]);
   }
   __syncthreads();
-  WAVE_MARK(5);
+  DC_MARK(g_wave_t, 5);
   if (i4 < k) {  // column i4 of U, normalised, by a quad
     const double dor = dd[org[i4]], tau = st[i4];
     double u[NT];
@@ -1230,7 +1181,7 @@ __global__ __launch_bounds__(256) void dc_wave_merge_kernel(double* __restrict__
     }
   }
   __syncthreads();
-  WAVE_MARK(6);
+  DC_MARK(g_wave_t, 6);
   // Q(lo + r, lo + c) = sum_j sQ(r, cs[j]) U(j, c) for c < k, sQ(r, cs[c]) for c >= k: lane = row,
   // wave wv owns columns wv NT .. wv NT + NT - 1 (accumulators in registers; U rows are
   // wave-uniform LDS reads)
@@ -1257,7 +1208,7 @@ __global__ __launch_bounds__(256) void dc_wave_merge_kernel(double* __restrict__
     }
     for (int c = k + wv; c < s; c += 4) qo[(long)c * ldq] = sQ[cs[c] * S + lane];
   }
-  WAVE_MARK(7);
+  DC_MARK(g_wave_t, 7);
 }
 
 int wave_merge_nc(int S) { return S <= 8 ? 8 : S <= 16 ? 16 : S <= 32 ? 32 : 64; }

@@ -20,15 +20,11 @@ namespace {
 
 constexpr int TB = 256;  // rows per block = threads per workgroup
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// block-wide sum of one value per thread (4 waves); result broadcast to every thread
+// block-wide sum of one value per thread (4 waves); result broadcast to every thread. Not
+// wave.h's block_sum_d_pre: that one reduces each wave on the DPP network and adds the
+// partials onto 0 in a loop, which would change this sum's bits.
 __device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wave_sum_f64(v);
+  v = wave_sum_d(v);
   const int w = threadIdx.x >> 6;
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[w] = v;
