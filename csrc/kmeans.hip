@@ -30,6 +30,7 @@
 //    per wave-instruction (the full-rate atomic shape on gfx950).
 #include "common.h"
 
+#include <atomic>
 #include <type_traits>
 
 namespace {
@@ -60,6 +61,11 @@ struct KMCfg {
 // the image stays lane-linear for global_load_lds (the swizzle is applied to the SOURCE).
 template <class C>
 __device__ __forceinline__ void stage_dma(const __bf16* __restrict__ cm2, int tile, char* lds, int wave, int lane) {
+  // wave is a scalar at every call: the piece index, its LDS destination and the test for a
+  // last partial round are scalars too, and the source is a scalar tile pointer plus one
+  // 32-bit lane offset per piece (as 64-bit pointers the offsets take two VGPRs each, held
+  // across the stage loop)
+  const char* gsrc = (const char*)cm2 + (size_t)tile * C::TILE_BYTES;
 #pragma unroll
   for (int j0 = 0; j0 < C::DMA_INSTR; j0 += C::WAVES) {
     const int j = j0 + wave;
@@ -68,8 +74,9 @@ __device__ __forceinline__ void stage_dma(const __bf16* __restrict__ cm2, int ti
       const int row = q / C::CPR;
       int c = q - row * C::CPR - ((row >> 3) & 1);
       if (c < 0) c += C::CPR;
-      const __bf16* src = cm2 + ((size_t)tile * C::TILE + row) * C::DP + c * 8;
-      __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
+      unsigned lo = (unsigned)(row * C::CPR + c) * 16u;
+      asm("" : "+v"(lo));  // keeps the zero-extension beside the load (kernel comment, ring sweep)
+      __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(gsrc + (size_t)lo),
                                        (void __attribute__((address_space(3)))*)(lds + j * 1024), 16, 0, 0);
     }
   }
@@ -93,356 +100,404 @@ template <int KS, int G, int WAVES, int RG, int PIPE, int PRIO = 0, int KEYLESS 
 __global__ __launch_bounds__(WAVES * 64) void kmeans_assign_kernel(
     const __bf16* __restrict__ X, long ldx, const __bf16* __restrict__ Cm2, long N, int ntiles, int tail_rg,
     int dcount, int* __restrict__ labels, float* __restrict__ sums, int ld_sums, float* __restrict__ obj_partial,
-    float* __restrict__ mind) {
+    float* __restrict__ mind, long nblk, unsigned* __restrict__ next_block) {
   using C = KMCfg<KS, G, WAVES, RG>;
   constexpr int NSLOT = RING ? 3 : 2;  // LDS slots of one centroid tile each
   static_assert(!RING || (KEYLESS && PIPE > 0 && G == 4 && RG == 4 && WAVES == 8 && KS <= 8),
                 "the ring sweep is written for the keyless 4 x 4-item stage of 8 waves");
-  __shared__ __attribute__((aligned(16))) char smem[NSLOT * C::TILE_BYTES + WAVES * 4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int srot = (r >> 3) & 1;
-  const long pbase = ((long)blockIdx.x * WAVES + wave) * (G * 32);
-
+  __shared__ __attribute__((aligned(16))) char smem[NSLOT * C::TILE_BYTES + WAVES * 4 + 16];
   // PRIO (variant 15): static VALU-arbitration priority for the younger half of the
   // workgroup, set once (MI355X_MICROARCH.md, two waves per SIMD, item 4)
   if constexpr (PRIO)
-    if (__builtin_amdgcn_readfirstlane(tid) >= WAVES * 32) __builtin_amdgcn_s_setprio(1);
-  // kick off the first centroid tile before loading this wave's points
-  stage_dma<C>(Cm2, 0, smem, wave, lane);
-  // ring: the second tile too (with one tile, that tile again: slot 1 is then never used, but
-  // the chain the last stage starts for a stage that does not exist reads written memory)
-  if constexpr (RING) stage_dma<C>(Cm2, ntiles > 1 ? 1 : 0, smem + C::TILE_BYTES, wave, lane);
+    if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) >= WAVES * 32) __builtin_amdgcn_s_setprio(1);
 
-  // ---- this wave's points: B-operand fragments, resident for the whole sweep
-  bf16x8 xf[G][KS];
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    long p = pbase + g * 32 + r;
-    if (p > N - 1) p = N - 1;
-    const bf16x8* row = (const bf16x8*)(X + p * ldx);
-#pragma unroll
-    for (int s = 0; s < KS; ++s) xf[g][s] = row[2 * s + h];
-  }
-
-  float best[G];
-  int bestt[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) { best[g] = KM_BIG; bestt[g] = 0; }
-  // argmin of one 32x32 tile into (best, bestt)[g]: the 16 candidates' register index rides
-  // in the low mantissa bits (one v_and_or per candidate). A plain v_min3 with the index
-  // searched only on improvement measured 5 % slower (it spills; profiles/r2_ktail).
-  // KEYLESS (variant 16): the plain minimum of the 16 candidates, no index bits. The sweep then
-  // knows only the winning 32-row group; the row inside it is found by the gather-sum pass,
-  // which re-computes that one group's 32 distances per point (kmeans_resolve.hip). Its min
-  // chain starts from best[g] itself: eight v_min3, one compare and one select per tile (10
-  // VALU, 1.56 per MFMA at 7 k-steps) where the minimum of the 16 first and a compare against
-  // best[g] after took 13 (profiles/r9_sweep_pipe). The keyed form stays: folded the same way
-  // its RG=2 tiling (variant 13) spills at 7 k-steps.
-  auto tile_argmin = [&](const floatx16& ac, int g, int tg) {
-    if constexpr (KEYLESS) {
-      float nb = best[g];
-#pragma unroll
-      for (int q = 0; q < 16; q += 2) nb = fminf(fminf(nb, ac[q]), ac[q + 1]);
-      if (nb < best[g]) bestt[g] = tg;
-      best[g] = nb;
-    } else {
-      float m = keyed(ac[0], 0u);
-#pragma unroll
-      for (int q = 1; q < 16; ++q) m = fminf(m, keyed(ac[q], (unsigned)q));
-      if (m < best[g]) { best[g] = m; bestt[g] = tg; }
-    }
-  };
-
-  // per-lane byte offsets of its A-fragment chunks inside a 32-row group
-  int aoff[KS];
-#pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    int cp = 2 * s + h + srot;
-    if (cp >= C::CPR) cp -= C::CPR;
-    aoff[s] = (r * C::CPR + cp) * 16;
-  }
-
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  // full tiles; a last tile of only tail_rg (< RG) row groups runs after the loop
-  const int nfull = tail_rg ? ntiles - 1 : ntiles;
-  if constexpr (RING) {
-    // The ring sweep (variant 16): the item pipeline of the two-slot body below run as ONE
-    // stream over all full stages, with nothing at a stage edge that is not also inside a stage.
-    //  * Three LDS slots, tile t in slot t % 3. One barrier per stage, at item 3. In front of it
-    //    a wave waits for its own pieces of tile t + 1 (requested during stage t - 1; tiles 0
-    //    and 1 in the prologue), so behind the barrier of stage t
-    //      - tile t + 1 is visible to every wave: its first read is at item 14 of stage t;
-    //      - every wave has left stage t - 1 (it passed that stage's item 15 to get here; the
-    //        stage's last read of its own slot is at item 10), so slot (t - 1) % 3 = (t + 2) % 3
-    //        is free:
-    //        the pieces of tile t + 2 go there, one per item, behind that barrier and in front
-    //        of the barrier of stage t + 1, which orders them against their first read.
-    //    Past the last tile the request repeats the last tile, into a slot nothing reads again
-    //    (the two live slots are t % 3 and (t + 1) % 3): no branch inside the item stream.
-    //  * Row group 0 of stage t + 1 is read under the last chain of stage t like any next row
-    //    group, and the chain of (stage t + 1, item 0) stands in front of the epilogue of
-    //    (stage t, item 15): accumulator and A fragments are carried over the loop edge. The
-    //    last stage starts such a chain for a stage that is not there (a tail tile's first
-    //    items, or a copy of the last tile); its result is dropped, so the one drain is at
-    //    the end of the sweep, in front of the tail tile.
-    //  * Address registers: two carried per-lane LDS bases and immediate ds_read offsets
-    //    (aoff[s] = aoff[0] + 32 s except the last chunk of the rotated rows, which wraps: the
-    //    second base), a scalar tile pointer plus one 32-bit lane offset per piece, scalar LDS
-    //    destinations.
-    //  * Every item is fenced (r9's hand-over: five MFMAs of chain i + 1, a hard fence, then
-    //    epilogue i over the rest): unfenced, hipcc reads the next row group's fragments in
-    //    front of the chain that still uses their registers and the 7 k-step instance spills.
-    // The k order of a chain and the group order of the min chain are the two-slot body's: labels
-    // are bit-identical (profiles/r10_sweep_ring).
-    constexpr int NI = RG * G, RGB = 32 * C::CPR * 16, HALF = WAVES / 2, HEAD = KS < 5 ? KS : 5;
+  // The grid is resident (launch_assign: at most as many workgroups as the device holds at
+  // once) and each workgroup runs point blocks until none is left: its own index first, then
+  // whatever *next_block (zeroed by the host in stream order) hands out, taken by one lane at
+  // the head of the block's epilogue. A block starts exactly as a freshly launched workgroup
+  // would (nothing of the sweep is carried over a block edge). A static stride b += gridDim.x
+  // measured slower than one workgroup per block: the CUs do not run at one speed
+  // (profiles/kmeans_slots).
+  long b = blockIdx.x;
+  while (b < nblk) {
+    // The thread id is opaque per block: everything per lane below is derived again for every
+    // block, as a new workgroup would. Derived once in front of the loop, the address arithmetic
+    // of the block's prologue and epilogue is hoisted and held in VGPRs across the sweep (10 to 24
+    // more per instantiation; the keyed 6 to 8 k-step instances then spill).
+    int tid = threadIdx.x;
+    long nb = N;  // (the point count too: N - 1 is otherwise kept in a VGPR pair for the clamp)
+    asm volatile("" : "+v"(tid), "+s"(nb));
+    const int lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int srot = (r >> 3) & 1;
+    // the block index and the wave's first point are scalars
     const int swave = __builtin_amdgcn_readfirstlane(wave);
-    unsigned loff[4];  // byte offset of this lane's 16 B inside a tile, per piece round
+    const long pbase = (b * WAVES + swave) * (G * 32);
+    // kick off the first centroid tile before loading this wave's points
+    stage_dma<C>(Cm2, 0, smem, swave, lane);
+    // ring: the second tile too (with one tile, that tile again: slot 1 is then never used, but
+    // the chain the last stage starts for a stage that does not exist reads written memory)
+    if constexpr (RING) stage_dma<C>(Cm2, ntiles > 1 ? 1 : 0, smem + C::TILE_BYTES, swave, lane);
+
+    // ---- this wave's points: B-operand fragments, resident for the whole sweep
+    bf16x8 xf[G][KS];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int q = (p * WAVES + wave) * 64 + lane;
-      const int row = q / C::CPR;
-      int c = q - row * C::CPR - ((row >> 3) & 1);
-      if (c < 0) c += C::CPR;
-      loff[p] = (unsigned)(row * C::CPR + c) * 16u;
+    for (int g = 0; g < G; ++g) {
+      long p = pbase + g * 32 + r;
+      if (p > nb - 1) p = nb - 1;
+      const bf16x8* row = (const bf16x8*)(X + p * ldx);
+#pragma unroll
+      for (int s = 0; s < KS; ++s) xf[g][s] = row[2 * s + h];
     }
-    auto sweep = [&](auto htag) {
-      constexpr int H = decltype(htag)::value;
-      int cur = 0, nxt = C::TILE_BYTES, nn = 2 * C::TILE_BYTES;  // slot byte offsets
-      // the lane's LDS read bases, carried: they move to the next slot in front of the reads
-      // of item 14 (an add of a scalar), the row group inside the slot is an immediate offset
-      int ab = aoff[0], abL = aoff[KS - 1] - 32 * (KS - 1);
-      auto a_read = [&](int imm, int s) { return *(const bf16x8*)(smem + (s == KS - 1 ? abL : ab) + (imm + 32 * s)); };
-      bf16x8 af[2][KS];
-      floatx16 acc[2];
-      // k-steps s0 .. s1 - 1 of item j's chain into acc[j & 1]. Under the last point group of a
-      // row group each A fragment of the next row group (of the next stage's first, from the
-      // next slot) is read right behind the MFMA of the same k-step: pinned there by the
-      // fences below the fragments need no third buffer
-      auto chain = [&](int j, int s0, int s1) {
-        const int rgj = j / G, gj = j % G;
-        floatx16& a = acc[j & 1];
-        if (s0 == 0) {
+
+    float best[G];
+    int bestt[G];
 #pragma unroll
-          for (int q = 0; q < 16; ++q) a[q] = 0.f;
-          if (gj == G - 1 && rgj + 1 == RG) {
-            ab += nxt - cur;
-            abL += nxt - cur;
+    for (int g = 0; g < G; ++g) { best[g] = KM_BIG; bestt[g] = 0; }
+    // argmin of one 32x32 tile into (best, bestt)[g]: the 16 candidates' register index rides
+    // in the low mantissa bits (one v_and_or per candidate). A plain v_min3 with the index
+    // searched only on improvement measured 5 % slower (it spills; profiles/r2_ktail).
+    // KEYLESS (variant 16): the plain minimum of the 16 candidates, no index bits. The sweep then
+    // knows only the winning 32-row group; the row inside it is found by the gather-sum pass,
+    // which re-computes that one group's 32 distances per point (kmeans_resolve.hip). Its min
+    // chain starts from best[g] itself: eight v_min3, one compare and one select per tile (10
+    // VALU, 1.56 per MFMA at 7 k-steps) where the minimum of the 16 first and a compare against
+    // best[g] after took 13 (profiles/r9_sweep_pipe). The keyed form stays: folded the same way
+    // its RG=2 tiling (variant 13) spills at 7 k-steps.
+    auto tile_argmin = [&](const floatx16& ac, int g, int tg) {
+      if constexpr (KEYLESS) {
+        float nb = best[g];
+#pragma unroll
+        for (int q = 0; q < 16; q += 2) nb = fminf(fminf(nb, ac[q]), ac[q + 1]);
+        if (nb < best[g]) bestt[g] = tg;
+        best[g] = nb;
+      } else {
+        float m = keyed(ac[0], 0u);
+#pragma unroll
+        for (int q = 1; q < 16; ++q) m = fminf(m, keyed(ac[q], (unsigned)q));
+        if (m < best[g]) { best[g] = m; bestt[g] = tg; }
+      }
+    };
+
+    // per-lane byte offsets of its A-fragment chunks inside a 32-row group
+    int aoff[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      int cp = 2 * s + h + srot;
+      if (cp >= C::CPR) cp -= C::CPR;
+      aoff[s] = (r * C::CPR + cp) * 16;
+    }
+    // aoff[s] = aoff[0] + 32 s except for the last chunk, which wraps in the rotated rows: two
+    // per-lane bases and immediate offsets address every fragment (KS offsets held across the
+    // sweep are five more VGPRs at 7 k-steps, and the keyed instances there have none to spare)
+    const int aoff0 = aoff[0], aoffL = aoff[KS - 1] - 32 * (KS - 1);
+    auto a_frag = [&](const char* base, int s) {
+      return *(const bf16x8*)(base + (s == KS - 1 ? aoffL : aoff0) + 32 * s);
+    };
+
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    // full tiles; a last tile of only tail_rg (< RG) row groups runs after the loop
+    const int nfull = tail_rg ? ntiles - 1 : ntiles;
+    if constexpr (RING) {
+      // The ring sweep (variant 16): the item pipeline of the two-slot body below run as ONE
+      // stream over all full stages, with nothing at a stage edge that is not also inside a stage.
+      //  * Three LDS slots, tile t in slot t % 3. One barrier per stage, at item 3. In front of it
+      //    a wave waits for its own pieces of tile t + 1 (requested during stage t - 1; tiles 0
+      //    and 1 in the prologue), so behind the barrier of stage t
+      //      - tile t + 1 is visible to every wave: its first read is at item 14 of stage t;
+      //      - every wave has left stage t - 1 (it passed that stage's item 15 to get here; the
+      //        stage's last read of its own slot is at item 10), so slot (t - 1) % 3 = (t + 2) % 3
+      //        is free:
+      //        the pieces of tile t + 2 go there, one per item, behind that barrier and in front
+      //        of the barrier of stage t + 1, which orders them against their first read.
+      //    Past the last tile the request repeats the last tile, into a slot nothing reads again
+      //    (the two live slots are t % 3 and (t + 1) % 3): no branch inside the item stream.
+      //  * Row group 0 of stage t + 1 is read under the last chain of stage t like any next row
+      //    group, and the chain of (stage t + 1, item 0) stands in front of the epilogue of
+      //    (stage t, item 15): accumulator and A fragments are carried over the loop edge. The
+      //    last stage starts such a chain for a stage that is not there (a tail tile's first
+      //    items, or a copy of the last tile); its result is dropped, so the one drain is at
+      //    the end of the sweep, in front of the tail tile.
+      //  * Address registers: two carried per-lane LDS bases and immediate ds_read offsets
+      //    (aoff[s] = aoff[0] + 32 s except the last chunk of the rotated rows, which wraps: the
+      //    second base), a scalar tile pointer plus one 32-bit lane offset per piece, scalar LDS
+      //    destinations.
+      //  * Every item is fenced (r9's hand-over: five MFMAs of chain i + 1, a hard fence, then
+      //    epilogue i over the rest): unfenced, hipcc reads the next row group's fragments in
+      //    front of the chain that still uses their registers and the 7 k-step instance spills.
+      // The k order of a chain and the group order of the min chain are the two-slot body's: labels
+      // are bit-identical (profiles/r10_sweep_ring).
+      constexpr int NI = RG * G, RGB = 32 * C::CPR * 16, HALF = WAVES / 2, HEAD = KS < 5 ? KS : 5;
+      unsigned loff[4];  // byte offset of this lane's 16 B inside a tile, per piece round
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int q = (p * WAVES + wave) * 64 + lane;
+        const int row = q / C::CPR;
+        int c = q - row * C::CPR - ((row >> 3) & 1);
+        if (c < 0) c += C::CPR;
+        loff[p] = (unsigned)(row * C::CPR + c) * 16u;
+      }
+      auto sweep = [&](auto htag) {
+        constexpr int H = decltype(htag)::value;
+        int cur = 0, nxt = C::TILE_BYTES, nn = 2 * C::TILE_BYTES;  // slot byte offsets
+        // the lane's LDS read bases, carried: they move to the next slot in front of the reads
+        // of item 14 (an add of a scalar), the row group inside the slot is an immediate offset
+        int ab = aoff0, abL = aoffL;
+        auto a_read = [&](int imm, int s) { return *(const bf16x8*)(smem + (s == KS - 1 ? abL : ab) + (imm + 32 * s)); };
+        bf16x8 af[2][KS];
+        floatx16 acc[2];
+        // k-steps s0 .. s1 - 1 of item j's chain into acc[j & 1]. Under the last point group of a
+        // row group each A fragment of the next row group (of the next stage's first, from the
+        // next slot) is read right behind the MFMA of the same k-step: pinned there by the
+        // fences below the fragments need no third buffer
+        auto chain = [&](int j, int s0, int s1) {
+          const int rgj = j / G, gj = j % G;
+          floatx16& a = acc[j & 1];
+          if (s0 == 0) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) a[q] = 0.f;
+            if (gj == G - 1 && rgj + 1 == RG) {
+              ab += nxt - cur;
+              abL += nxt - cur;
+            }
           }
-        }
 #pragma unroll
-        for (int s = s0; s < s1; ++s) {
-          a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[rgj & 1][s], xf[gj][s], a, 0, 0, 0);
-          if (gj == G - 1) af[(rgj + 1) & 1][s] = a_read(rgj + 1 < RG ? (rgj + 1) * RGB : 0, s);
+          for (int s = s0; s < s1; ++s) {
+            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[rgj & 1][s], xf[gj][s], a, 0, 0, 0);
+            if (gj == G - 1) af[(rgj + 1) & 1][s] = a_read(rgj + 1 < RG ? (rgj + 1) * RGB : 0, s);
+          }
+        };
+#pragma unroll
+        for (int s = 0; s < KS; ++s) af[0][s] = a_read(0, s);
+        chain(0, 0, KS);
+        __builtin_amdgcn_sched_barrier(0);
+        for (int t = 0; t < nfull; ++t) {
+          const int tq = t + 2 < ntiles ? t + 2 : ntiles - 1;
+          const char* gsrc = (const char*)Cm2 + (size_t)tq * C::TILE_BYTES;
+#pragma unroll
+          for (int i = 0; i < NI; ++i) {
+            const int rg = i / G, g = i % G;
+            // the first HEAD MFMAs of chain i + 1 stand behind a hard fence, in front of every
+            // VALU of epilogue i: with five in front the hazard wait of the epilogue's head is
+            // out of the stream (profiles/r9_sweep_pipe)
+            chain((i + 1) % NI, 0, HEAD);
+            __builtin_amdgcn_sched_barrier(0);
+            if (i == KM_RING_BARRIER_ITEM) {
+              asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+              __syncthreads();
+            }
+            constexpr int NP = (C::DMA_INSTR - H * HALF + WAVES - 1) / WAVES;  // piece rounds of this half
+            const int p = km_ring_piece_at(H, i);
+            if (p >= 0 && p < NP) {
+              // the empty asm keeps the zero-extension of the lane offset beside the load, where
+              // it folds into the scalar-base address form (hoisted out of the loop it becomes
+              // a 64-bit register pair and an add per piece)
+              unsigned lo = loff[p];
+              asm("" : "+v"(lo));
+              __builtin_amdgcn_global_load_lds(
+                  (const void __attribute__((address_space(1)))*)(gsrc + (size_t)lo),
+                  (void __attribute__((address_space(3)))*)(smem + nn + (p * WAVES + swave) * 1024), 16, 0, 0);
+            }
+            chain((i + 1) % NI, HEAD, KS);
+            tile_argmin(acc[i & 1], g, t * RG + rg);
+            // epilogue i (10 VALU) over the rest of chain i + 1, then a second fence
+            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+#pragma unroll
+            for (int s = HEAD; s < KS; ++s) {
+              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+              __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          const int o = cur;
+          cur = nxt;
+          nxt = nn;
+          nn = o;
         }
       };
+      if (nfull > 0) {
+        if (swave < HALF) sweep(std::integral_constant<int, 0>{});
+        else sweep(std::integral_constant<int, 1>{});
+      }
+      // the last stages' requests: none may land after the workgroup has gone
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else
+    for (int t = 0; t < nfull; ++t) {
+      if (t + 1 < ntiles) stage_dma<C>(Cm2, t + 1, smem + ((t + 1) & 1) * C::TILE_BYTES, swave, lane);
+      const char* buf = smem + (t & 1) * C::TILE_BYTES;
+      bf16x8 af[2][KS];
 #pragma unroll
-      for (int s = 0; s < KS; ++s) af[0][s] = a_read(0, s);
-      chain(0, 0, KS);
-      __builtin_amdgcn_sched_barrier(0);
-      for (int t = 0; t < nfull; ++t) {
-        const int tq = t + 2 < ntiles ? t + 2 : ntiles - 1;
-        const char* gsrc = (const char*)Cm2 + (size_t)tq * C::TILE_BYTES;
+      for (int s = 0; s < KS; ++s) af[0][s] = a_frag(buf, s);
+      if constexpr (PIPE > 0) {
+        // software pipeline over the stage's RG*G (row group, point group) items: the MFMA
+        // chain of item i+1 stands in front of the argmin epilogue of item i, so most of the
+        // epilogue's VALU work sits in the next chain's MFMA gaps. hipcc still puts the head of
+        // epilogue i and its hazard wait (s_nop 11) between the two chains; forcing five MFMAs of
+        // chain i+1 in front of it with a scheduling fence removes the wait from the stream and
+        // measured 0.6 ms of 132 (two waves share the SIMD's matrix pipe and fill each other's
+        // holes), too little to keep (profiles/r9_sweep_pipe)
+        constexpr int NI = RG * G;
+        floatx16 acc[2];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[0][q] = 0.f;
+#pragma unroll
+        for (int s = 0; s < KS; ++s) acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][s], xf[0][s], acc[0], 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
           const int rg = i / G, g = i % G;
-          // the first HEAD MFMAs of chain i + 1 stand behind a hard fence, in front of every
-          // VALU of epilogue i: with five in front the hazard wait of the epilogue's head is
-          // out of the stream (profiles/r9_sweep_pipe)
-          chain((i + 1) % NI, 0, HEAD);
-          __builtin_amdgcn_sched_barrier(0);
-          if (i == KM_RING_BARRIER_ITEM) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
+          if (g == 0 && rg + 1 < RG) {
+            // no LDS read crosses this point (everything else may): read any earlier, the
+            // fragments take a third buffer and the keyed 7 k-step instances spill 28 - 44 B
+            __builtin_amdgcn_sched_barrier(0x7F);
+            const char* nb = buf + (rg + 1) * 32 * C::CPR * 16;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) af[(rg + 1) & 1][s] = a_frag(nb, s);
           }
-          constexpr int NP = (C::DMA_INSTR - H * HALF + WAVES - 1) / WAVES;  // piece rounds of this half
-          const int p = km_ring_piece_at(H, i);
-          if (p >= 0 && p < NP) {
-            // the empty asm keeps the zero-extension of the lane offset beside the load, where
-            // it folds into the scalar-base address form (hoisted out of the loop it becomes
-            // a 64-bit register pair and an add per piece)
-            unsigned lo = loff[p];
-            asm("" : "+v"(lo));
-            __builtin_amdgcn_global_load_lds(
-                (const void __attribute__((address_space(1)))*)(gsrc + (size_t)lo),
-                (void __attribute__((address_space(3)))*)(smem + nn + (p * WAVES + swave) * 1024), 16, 0, 0);
+          if (i + 1 < NI) {
+            const int rg1 = (i + 1) / G, g1 = (i + 1) % G;
+            floatx16& an = acc[(i + 1) & 1];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) an[q] = 0.f;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) an = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[rg1 & 1][s], xf[g1][s], an, 0, 0, 0);
           }
-          chain((i + 1) % NI, HEAD, KS);
           tile_argmin(acc[i & 1], g, t * RG + rg);
-          // epilogue i (10 VALU) over the rest of chain i + 1, then a second fence
-          __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+          if constexpr (PIPE == 2) {
 #pragma unroll
-          for (int s = HEAD; s < KS; ++s) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+            for (int s = 0; s < KS; ++s) {
+              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
+              __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);  // then up to 4 VALU
+            }
           }
-          __builtin_amdgcn_sched_barrier(0);
         }
-        const int o = cur;
-        cur = nxt;
-        nxt = nn;
-        nn = o;
-      }
-    };
-    if (nfull > 0) {
-      if (swave < HALF) sweep(std::integral_constant<int, 0>{});
-      else sweep(std::integral_constant<int, 1>{});
-    }
-    // the last stages' requests: none may land after the workgroup has gone
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else
-  for (int t = 0; t < nfull; ++t) {
-    if (t + 1 < ntiles) stage_dma<C>(Cm2, t + 1, smem + ((t + 1) & 1) * C::TILE_BYTES, wave, lane);
-    const char* buf = smem + (t & 1) * C::TILE_BYTES;
-    bf16x8 af[2][KS];
+      } else
 #pragma unroll
-    for (int s = 0; s < KS; ++s) af[0][s] = *(const bf16x8*)(buf + aoff[s]);
-    if constexpr (PIPE > 0) {
-      // software pipeline over the stage's RG*G (row group, point group) items: the MFMA
-      // chain of item i+1 stands in front of the argmin epilogue of item i, so most of the
-      // epilogue's VALU work sits in the next chain's MFMA gaps. hipcc still puts the head of
-      // epilogue i and its hazard wait (s_nop 11) between the two chains; forcing five MFMAs of
-      // chain i+1 in front of it with a scheduling fence removes the wait from the stream and
-      // measured 0.6 ms of 132 (two waves share the SIMD's matrix pipe and fill each other's
-      // holes), too little to keep (profiles/r9_sweep_pipe)
-      constexpr int NI = RG * G;
-      floatx16 acc[2];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[0][q] = 0.f;
-#pragma unroll
-      for (int s = 0; s < KS; ++s) acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][s], xf[0][s], acc[0], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        const int rg = i / G, g = i % G;
-        if (g == 0 && rg + 1 < RG) {
+      for (int rg = 0; rg < RG; ++rg) {
+        if (rg + 1 < RG) {
           const char* nb = buf + (rg + 1) * 32 * C::CPR * 16;
 #pragma unroll
-          for (int s = 0; s < KS; ++s) af[(rg + 1) & 1][s] = *(const bf16x8*)(nb + aoff[s]);
+          for (int s = 0; s < KS; ++s) af[(rg + 1) & 1][s] = a_frag(nb, s);
         }
-        if (i + 1 < NI) {
-          const int rg1 = (i + 1) / G, g1 = (i + 1) % G;
-          floatx16& an = acc[(i + 1) & 1];
+        const int tg = t * RG + rg;
 #pragma unroll
-          for (int q = 0; q < 16; ++q) an[q] = 0.f;
+        for (int g = 0; g < G; ++g) {
+          floatx16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int s = 0; s < KS; ++s) an = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[rg1 & 1][s], xf[g1][s], an, 0, 0, 0);
+          for (int s = 0; s < KS; ++s)
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[rg & 1][s], xf[g][s], acc, 0, 0, 0);
+          tile_argmin(acc, g, tg);
         }
-        tile_argmin(acc[i & 1], g, t * RG + rg);
-        if constexpr (PIPE == 2) {
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
+    if (tail_rg) {
+      // K not a multiple of the stage: only the live 32-row groups of the last tile (its DMA
+      // landed with the previous stage's wait + barrier; the rows past them are never read)
+      const int t = ntiles - 1;
+      const char* buf = smem + (t % NSLOT) * C::TILE_BYTES;
+      for (int rg = 0; rg < tail_rg; ++rg) {
+        const char* nb = buf + rg * 32 * C::CPR * 16;
+        bf16x8 af[KS];
 #pragma unroll
-          for (int s = 0; s < KS; ++s) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
-            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);  // then up to 4 VALU
+        for (int s = 0; s < KS; ++s) af[s] = a_frag(nb, s);
+        const int tg = t * RG + rg;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          floatx16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s], xf[g][s], acc, 0, 0, 0);
+          tile_argmin(acc, g, tg);
+        }
+      }
+    }
+
+    // ---- resolve argmin across the two lane halves, write labels / objective partials (the
+    // keyed half exchange and the row decode stand in both wide kernels too: change all three)
+    // (the lane's ids are derived again from the thread id, so none of them is held over the sweep)
+    {
+      int tid = threadIdx.x;
+      asm volatile("" : "+v"(tid));
+      const int lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+      // the next block of this workgroup; the answer arrives under the epilogue
+      unsigned* nextw = (unsigned*)(smem + NSLOT * C::TILE_BYTES + WAVES * 4);
+      unsigned fetched = 0;
+      if (tid == 0) fetched = gridDim.x + atomicAdd(next_block, 1u);
+      // __shfl_xor with this lane id (its own is a hoisted VGPR as well)
+      auto lane_xor = [&](auto v, int o) {
+        return __builtin_bit_cast(decltype(v), __builtin_amdgcn_ds_bpermute((lane ^ o) << 2, __builtin_bit_cast(int, v)));
+      };
+      int lab[G];
+      float local_obj = 0.f;
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        float xs = 0.f;
+#pragma unroll
+        for (int s = 0; s < KS; ++s)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const float v = (float)xf[g][s][j];
+            xs = fmaf(v, v, xs);
+          }
+        xs += lane_xor(xs, 32);
+        xs -= (float)KM_ONES;  // the 1.0 columns of X
+        const float ob = lane_xor(best[g], 32);
+        const int obt = lane_xor(bestt[g], 32);
+        // keyless: the smaller value, on equality the lower group (both halves agree)
+        const bool take = KEYLESS ? (ob < best[g] || (ob == best[g] && obt < bestt[g]))
+                                  : (h ? (ob <= best[g]) : (ob < best[g]));
+        const float bv = take ? ob : best[g];
+        const int bt = take ? obt : bestt[g];
+        const int hw = take ? (1 - h) : h;
+        const unsigned reg = __float_as_uint(bv) & 0xFu;
+        // keyless: labels[p] is the winning 32-row group id, 0 .. swept_k / 32 - 1
+        const int idx = KEYLESS ? bt : bt * 32 + (int)(reg & 3u) + 8 * (int)(reg >> 2) + 4 * hw;
+        lab[g] = idx;
+        const long p = pbase + g * 32 + r;
+        if (h == 0 && p < nb) {
+          labels[p] = idx;
+          // keyed: the distance without the index bits in its low mantissa (exact where the
+          // products are: those four bits of the candidate were cleared when the index went in)
+          const float bd = KEYLESS ? bv : __uint_as_float(__float_as_uint(bv) & ~0xFu);
+          local_obj += fmaxf(bd + xs, 0.f);
+          if (mind) mind[p] = bd + xs;  // squared distance to the chosen centroid (rotation merge)
+        }
+      }
+      if (obj_partial) {
+        for (int o = 32; o > 0; o >>= 1) local_obj += lane_xor(local_obj, o);  // wave_sum's order
+        float* red = (float*)(smem + NSLOT * C::TILE_BYTES);
+        if (lane == 0) red[wave] = local_obj;
+        __syncthreads();
+        if (tid == 0) {
+          float acc = 0.f;
+#pragma unroll
+          for (int w = 0; w < WAVES; ++w) acc += red[w];
+          obj_partial[b] = acc;
+        }
+      }
+
+      // ---- accumulate (x, 1) rows into the per-centroid partial sums
+      if (!KEYLESS && sums) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          for (int i = 0; i < 32; ++i) {
+            const long p = pbase + g * 32 + i;
+            if (p >= nb) break;
+            const int l = __shfl(lab[g], i, 64);
+            const __bf16* xr = X + p * ldx;
+            float* sr = sums + (long)l * ld_sums;
+            for (int c = lane; c <= dcount; c += 64) atomicAdd(sr + c, (float)xr[c]);
           }
         }
       }
-    } else
-#pragma unroll
-    for (int rg = 0; rg < RG; ++rg) {
-      if (rg + 1 < RG) {
-        const char* nb = buf + (rg + 1) * 32 * C::CPR * 16;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) af[(rg + 1) & 1][s] = *(const bf16x8*)(nb + aoff[s]);
-      }
-      const int tg = t * RG + rg;
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        floatx16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[rg & 1][s], xf[g][s], acc, 0, 0, 0);
-        tile_argmin(acc, g, tg);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-  if (tail_rg) {
-    // K not a multiple of the stage: only the live 32-row groups of the last tile (its DMA
-    // landed with the previous stage's wait + barrier; the rows past them are never read)
-    const int t = ntiles - 1;
-    const char* buf = smem + (t % NSLOT) * C::TILE_BYTES;
-    for (int rg = 0; rg < tail_rg; ++rg) {
-      const char* nb = buf + rg * 32 * C::CPR * 16;
-      bf16x8 af[KS];
-#pragma unroll
-      for (int s = 0; s < KS; ++s) af[s] = *(const bf16x8*)(nb + aoff[s]);
-      const int tg = t * RG + rg;
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        floatx16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s], xf[g][s], acc, 0, 0, 0);
-        tile_argmin(acc, g, tg);
-      }
-    }
-  }
-
-  // ---- resolve argmin across the two lane halves, write labels / objective partials (the
-  // keyed half exchange and the row decode stand in both wide kernels too: change all three)
-  int lab[G];
-  float local_obj = 0.f;
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    float xs = 0.f;
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float v = (float)xf[g][s][j];
-        xs = fmaf(v, v, xs);
-      }
-    xs += __shfl_xor(xs, 32, 64);
-    xs -= (float)KM_ONES;  // the 1.0 columns of X
-    const float ob = __shfl_xor(best[g], 32, 64);
-    const int obt = __shfl_xor(bestt[g], 32, 64);
-    // keyless: the smaller value, on equality the lower group (both halves agree)
-    const bool take = KEYLESS ? (ob < best[g] || (ob == best[g] && obt < bestt[g]))
-                              : (h ? (ob <= best[g]) : (ob < best[g]));
-    const float bv = take ? ob : best[g];
-    const int bt = take ? obt : bestt[g];
-    const int hw = take ? (1 - h) : h;
-    const unsigned reg = __float_as_uint(bv) & 0xFu;
-    // keyless: labels[p] is the winning 32-row group id, 0 .. swept_k / 32 - 1
-    const int idx = KEYLESS ? bt : bt * 32 + (int)(reg & 3u) + 8 * (int)(reg >> 2) + 4 * hw;
-    lab[g] = idx;
-    const long p = pbase + g * 32 + r;
-    if (h == 0 && p < N) {
-      labels[p] = idx;
-      // keyed: the distance without the index bits in its low mantissa (exact where the
-      // products are: those four bits of the candidate were cleared when the index went in)
-      const float bd = KEYLESS ? bv : __uint_as_float(__float_as_uint(bv) & ~0xFu);
-      local_obj += fmaxf(bd + xs, 0.f);
-      if (mind) mind[p] = bd + xs;  // squared distance to the chosen centroid (rotation merge)
-    }
-  }
-  if (obj_partial) {
-    local_obj = wave_sum(local_obj);
-    float* red = (float*)(smem + NSLOT * C::TILE_BYTES);
-    if (lane == 0) red[wave] = local_obj;
-    __syncthreads();
-    if (tid == 0) {
-      float acc = 0.f;
-#pragma unroll
-      for (int w = 0; w < WAVES; ++w) acc += red[w];
-      obj_partial[blockIdx.x] = acc;
-    }
-  }
-
-  // ---- accumulate (x, 1) rows into the per-centroid partial sums
-  if (!KEYLESS && sums) {
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      for (int i = 0; i < 32; ++i) {
-        const long p = pbase + g * 32 + i;
-        if (p >= N) break;
-        const int l = __shfl(lab[g], i, 64);
-        const __bf16* xr = X + p * ldx;
-        float* sr = sums + (long)l * ld_sums;
-        for (int c = lane; c <= dcount; c += 64) atomicAdd(sr + c, (float)xr[c]);
-      }
+      // One barrier per block edge: behind it the block's last reads of the LDS slots (the tail tile
+      // sits in slot (ntiles - 1) % NSLOT, which the next block's first tile overwrites) and of
+      // red[] are done, and every wave sees the next block's index
+      if (tid == 0) *nextw = fetched;
+      __syncthreads();
+      b = (long)(unsigned)__builtin_amdgcn_readfirstlane((int)*nextw);
     }
   }
 }
@@ -920,6 +975,49 @@ __global__ __launch_bounds__(256) void kmeans_wide_finish_kernel(const unsigned 
   if (threadIdx.x == 0 && obj_partial) obj_partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
+// harp_kmeans_set_resident_blocks: 0 = every instantiation's own resident grid
+std::atomic<int> km_resident_override{0};
+
+// The words the resident grids take their next point block from, one per launch in flight:
+// launches take them round robin and zero theirs in stream order in front of the kernel, so a
+// word is shared only by launches KM_NEXT_WORDS apart, which would have to overlap on two streams.
+constexpr int KM_NEXT_WORDS = 1024;
+__device__ unsigned km_next_block_words[KM_NEXT_WORDS];
+std::atomic<unsigned> km_next_word{0};
+
+// this launch's word, zeroed on the stream; nullptr if the runtime refuses
+unsigned* next_block_word(hipStream_t stream) {
+  unsigned* base = nullptr;
+  if (hipGetSymbolAddress((void**)&base, HIP_SYMBOL(km_next_block_words)) != hipSuccess || !base) return nullptr;
+  unsigned* w = base + km_next_word.fetch_add(1, std::memory_order_relaxed) % KM_NEXT_WORDS;
+  return hipMemsetAsync(w, 0, sizeof(unsigned), stream) == hipSuccess ? w : nullptr;
+}
+
+// Workgroups of one assign instantiation the current device holds at once: CUs x the
+// occupancy of that kernel (1 at 7 k-steps: 256 VGPRs and 86 KB of LDS), asked for once per
+// instantiation and device. 0 if the runtime cannot say.
+template <int KS, int G, int WAVES, int RG, int PIPE, int PRIO, int KEYLESS, int RINGK>
+int assign_resident_blocks() {
+  constexpr int MAXDEV = 64;
+  static std::atomic<int> cache[MAXDEV];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return 0;
+  int res = cache[dev].load(std::memory_order_relaxed);
+  if (res > 0) return res;
+  int per = 0, cus = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kmeans_assign_kernel<KS, G, WAVES, RG, PIPE, PRIO, KEYLESS, RINGK>,
+                                                   WAVES * 64, 0) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per <= 0 || cus <= 0)
+    return 0;
+  res = per * cus;
+  cache[dev].store(res, std::memory_order_relaxed);
+  return res;
+}
+
+// the ring sweep spills at 8 k-steps (660 B): that instance keeps the two-slot body
+template <int KS, int RING>
+constexpr int km_ring_at = RING && KS <= 7;
+
 template <int KS, int G, int WAVES, int RG, int PIPE = 0, int PRIO = 0, int KEYLESS = 0, int RING = 0>
 int launch_assign(const void* X, long ldx, const void* Cm2, long N, int Kp, int d, int* labels, float* sums,
                   int ld_sums, float* obj_partial, float* mind, hipStream_t stream) {
@@ -927,10 +1025,17 @@ int launch_assign(const void* X, long ldx, const void* Cm2, long N, int Kp, int 
   if (Kp % 32 || (KEYLESS && sums)) return HARP_EBADARG;  // no fused atomics in the keyless sweep
   const long nblk = (N + C::PTS - 1) / C::PTS;
   const int ntiles = (Kp + C::TILE - 1) / C::TILE, tail_rg = (Kp % C::TILE) / 32;
-  // the ring sweep spills at 8 k-steps (660 B): that instance keeps the two-slot body
-  constexpr int RINGK = RING && KS <= 7;
-  kmeans_assign_kernel<KS, G, WAVES, RG, PIPE, PRIO, KEYLESS, RINGK><<<dim3((unsigned)nblk), dim3(C::THREADS), 0, stream>>>(
-      (const __bf16*)X, ldx, (const __bf16*)Cm2, N, ntiles, tail_rg, d, labels, sums, ld_sums, obj_partial, mind);
+  constexpr int RINGK = km_ring_at<KS, RING>;
+  // a resident grid: the workgroups loop over the point blocks (kernel comment)
+  int resident = km_resident_override.load(std::memory_order_relaxed);
+  if (resident <= 0) resident = assign_resident_blocks<KS, G, WAVES, RG, PIPE, PRIO, KEYLESS, RINGK>();
+  if (resident <= 0) return HARP_ELAUNCH;
+  const long grid = nblk < resident ? nblk : resident;
+  if (nblk + grid >= (1L << 32)) return HARP_EUNSUPPORTED;  // block indices are handed out as 32-bit words
+  unsigned* next = next_block_word(stream);
+  if (!next) return HARP_ELAUNCH;
+  kmeans_assign_kernel<KS, G, WAVES, RG, PIPE, PRIO, KEYLESS, RINGK><<<dim3((unsigned)grid), dim3(C::THREADS), 0, stream>>>(
+      (const __bf16*)X, ldx, (const __bf16*)Cm2, N, ntiles, tail_rg, d, labels, sums, ld_sums, obj_partial, mind, nblk, next);
   return harp_launch_status();
 }
 
@@ -956,6 +1061,13 @@ int launch_assign(const void* X, long ldx, const void* Cm2, long N, int Kp, int 
   case V: return launch_assign<KS, G, WAVES, RG, PIPE, PRIO, KEYLESS, RING>(X, ldx, Cm2, N, Kp, d, labels, sums, ld, op, md, s);
 #define KM_PTS_ROW(KS, V, G, WAVES, RG, PIPE, PRIO, KEYLESS, RING) \
   case V: return KMCfg<KS, G, WAVES, RG>::PTS;
+#define KM_RESIDENT_ROW(KS, V, G, WAVES, RG, PIPE, PRIO, KEYLESS, RING) \
+  case V: return assign_resident_blocks<KS, G, WAVES, RG, PIPE, PRIO, KEYLESS, km_ring_at<KS, RING>>();
+#define KM_RESIDENT(KS)                      \
+  switch (variant) {                         \
+    KM_VARIANT_TABLE(KM_RESIDENT_ROW, KS)    \
+    default: return -1;                      \
+  }
 #define KM_VARIANTS(KS)                      \
   switch (variant) {                         \
     KM_VARIANT_TABLE(KM_LAUNCH_ROW, KS)      \
@@ -969,6 +1081,31 @@ HARP_EXPORT int harp_kmeans_points_per_block(int variant) {
     KM_VARIANT_TABLE(KM_PTS_ROW, 1)  // PTS does not depend on the k-steps
     default: return -1;
   }
+}
+
+// Workgroups harp_kmeans_assign launches at most for (variant, ksteps = dp / 16 in 1..8) on the
+// current device: the resident grid, which loops over the point blocks. 0 if the runtime
+// cannot say, -1 for a pair that is not in the table.
+HARP_EXPORT int harp_kmeans_resident_blocks(int variant, int ksteps) {
+  switch (ksteps) {
+    case 1: KM_RESIDENT(1)
+    case 2: KM_RESIDENT(2)
+    case 3: KM_RESIDENT(3)
+    case 4: KM_RESIDENT(4)
+    case 5: KM_RESIDENT(5)
+    case 6: KM_RESIDENT(6)
+    case 7: KM_RESIDENT(7)
+    case 8: KM_RESIDENT(8)
+    default: return -1;
+  }
+}
+
+// n > 0: every assign launch takes min(point blocks, n) workgroups (tests force 1, 2, 3);
+// 0: back to the resident grid. Process-wide.
+HARP_EXPORT int harp_kmeans_set_resident_blocks(int n) {
+  if (n < 0) return HARP_EBADARG;
+  km_resident_override.store(n, std::memory_order_relaxed);
+  return HARP_OK;
 }
 
 // X rows of dp (MFMA k) elements at a row stride of ldx >= dp elements (ldx % 8 == 0: 16-B

@@ -25,6 +25,8 @@ c_int, c_long, c_float, c_void_p, c_ulonglong, c_double = (
 # name -> argtypes (restype is always c_int status)
 _SIGNATURES = {
     "harp_kmeans_points_per_block": [c_int],
+    "harp_kmeans_resident_blocks": [c_int, c_int],
+    "harp_kmeans_set_resident_blocks": [c_int],
     "harp_kmeans_assign": [c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                            c_void_p, c_void_p, c_int, c_void_p],
     # X, ldx, Cm2, N, dp, kswept, kp, d, keys, variant, stream

@@ -36,7 +36,8 @@ ONES = 4  # X columns d..d+3 hold 1.0
 # profiles/r7_keyless, r9_sweep_pipe). Its sweep runs as one item stream over all stages: three
 # LDS slots, one barrier inside a stage, the next tiles requested one piece per item, nothing
 # drained at a stage edge (1..7 k-steps; profiles/r10_sweep_ring). Calls without a bucketed sum
-# to resolve in run 15.
+# to resolve in run 15. Every narrow variant runs as a resident grid whose workgroups take point
+# blocks from a device counter until none is left (profiles/kmeans_slots).
 DEFAULT_VARIANT = 16
 KEYLESS_VARIANT, KEYED_VARIANT = 16, 15
 KEYLESS_MAX_DP = 128
@@ -144,6 +145,17 @@ def prepare(c: torch.Tensor, dp: int, out: Optional[CentroidOperand] = None) -> 
     out.cn.fill_(1e38)
     out.cn[:K] = (c.double() ** 2).sum(1).float()
     return out
+
+
+def resident_blocks(variant: int, dp: int) -> int:
+    """Workgroups the narrow assign kernel launches at most for (variant, dp <= 128) on the
+    current device: its grid is resident and loops over the point blocks (csrc/kmeans.hip)."""
+    return _lib.kernels().harp_kmeans_resident_blocks(variant, dp // 16)
+
+
+def set_resident_blocks(n: int) -> None:
+    """Force the assign grid to min(point blocks, n) workgroups (tests); 0 = the resident grid."""
+    _lib.check(_lib.kernels().harp_kmeans_set_resident_blocks(n), "kmeans_set_resident_blocks")
 
 
 def swept_k(op: "CentroidOperand") -> int:
