@@ -128,6 +128,91 @@ __global__ __launch_bounds__(256) void bucket_kernel(const int* __restrict__ lab
   }
 }
 
+// ---- span-ordered form (harp_bucket_labels_spans) -------------------------------------
+// The points are cut into spans of `span` consecutive indices (a power of two) and sorted by
+// (span, label): bucket q = s * K + g holds the points of span s with label g, spans in order.
+// A chunk lies in one span, so the per-chunk histogram stays K wide; only the scans know about
+// spans. A column-scan segment is `seg` = min(SEG, chunks per span) chunks, a power of two, so
+// it lies in one span too.
+
+// level 1, as colscan1_kernel with a run-time segment length (segments on grid x: there may be
+// more than 65535 of them)
+__global__ void colscan1_spans_kernel(int* __restrict__ H, int nchunks, int K, int seg, int* __restrict__ T) {
+  const int k = blockIdx.y * blockDim.x + threadIdx.x;
+  const int s = blockIdx.x;
+  if (k >= K) return;
+  const int c0 = s * seg;
+  int c1 = c0 + seg;
+  if (c1 > nchunks) c1 = nchunks;
+  int run = 0;
+  for (int c = c0; c < c1; ++c) {
+    const int v = H[(long)c * K + k];
+    H[(long)c * K + k] = run;
+    run += v;
+  }
+  T[(long)s * K + k] = run;
+}
+
+// level 2: exclusive scan over the sps segments of span blockIdx.x (the scan restarts at
+// every span); counts[span * K + k] = rows of that bucket
+__global__ void colscan2_spans_kernel(int* __restrict__ T, int nseg, int sps, int K, int* __restrict__ counts) {
+  const int k = blockIdx.y * blockDim.x + threadIdx.x;
+  const int sp = blockIdx.x;
+  if (k >= K) return;
+  const int s0 = sp * sps;
+  int s1 = s0 + sps;
+  if (s1 > nseg) s1 = nseg;
+  int run = 0;
+  for (int s = s0; s < s1; ++s) {
+    const int v = T[(long)s * K + k];
+    T[(long)s * K + k] = run;
+    run += v;
+  }
+  counts[(long)sp * K + k] = run;
+}
+
+// bucket_kernel with the cursors of the chunk's span; rank (optional) receives every point's
+// sorted position, a coalesced store by the thread that read its label. Every chunk in flight
+// keeps K partly written lines of perm open in the L2, and what is evicted early goes out as
+// partial writes (at 256 threads and 65536-label chunks 41 M write requests for the 6 M lines
+// of perm at n = 1e8, K = 313). 1024 threads per chunk mean a quarter of the chunks in flight,
+// each done four times sooner: hist + scans + scatter 1.05 -> 0.83 ms with 16384-label chunks
+// (profiles/kmeans_tail_onepass/scatter_shape.json).
+constexpr int SPAN_TPB = 1024;
+constexpr long SPAN_CHUNK = 16384;  // most labels per chunk
+
+__global__ __launch_bounds__(SPAN_TPB) void bucket_spans_kernel(const int* __restrict__ lab, long n, int K,
+                                                                long chunk, int cps, int seg,
+                                                                const int* __restrict__ H, const int* __restrict__ T,
+                                                                const int* __restrict__ start, int* __restrict__ perm,
+                                                                int* __restrict__ rank) {
+  extern __shared__ __attribute__((aligned(16))) int cur[];
+  const int c = xcd_contiguous(blockIdx.x, gridDim.x), s = c / seg;
+  const int* st = start + (long)(c / cps) * K;
+  for (int k = threadIdx.x; k < K; k += blockDim.x) cur[k] = st[k] + T[(long)s * K + k] + H[(long)c * K + k];
+  __syncthreads();
+  const long a = (long)c * chunk;
+  long b = a + chunk;
+  if (b > n) b = n;
+  constexpr int U = 8;  // labels in flight per thread, as in bucket_kernel
+  for (long i0 = a + threadIdx.x; i0 < b; i0 += (long)U * blockDim.x) {
+    int l[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long i = i0 + (long)u * blockDim.x;
+      l[u] = i < b ? lab[i] : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (l[u] >= 0) {
+        const long i = i0 + (long)u * blockDim.x;
+        const int j = atomicAdd(&cur[l[u]], 1);
+        perm[j] = (int)i;
+        if (rank) rank[i] = j;
+      }
+  }
+}
+
 // Skew-proof gather-sum: every LPR-lane slot owns RUN consecutive entries of the
 // bucket-sorted permutation (so work is balanced whatever the bucket sizes), keeps the
 // running row sum in registers, and flushes it with one contiguous fp32 atomic row segment
@@ -323,6 +408,73 @@ HARP_EXPORT int harp_bucket_labels(const int* lab, long n, int K, int* ws, long*
   colscan2_kernel<<<dim3((K + 255) / 256), dim3(256), 0, s>>>(T, nseg, K, counts);
   segscan_kernel<<<dim3(1), dim3(1024), 0, s>>>(counts, K, start);
   bucket_kernel<<<dim3(nch), dim3(256), lds, s>>>(lab, n, K, chunk, H, T, start, perm);
+  return harp_launch_status();
+}
+
+namespace {
+
+struct SpanGeom {
+  long chunk;  // labels per chunk, min(harp_bucket_chunk(n), SPAN_CHUNK, span): a chunk lies in one span
+  int nch, cps, seg, nseg, sps, nspans;
+  long nb;     // composite buckets: nspans * K
+};
+
+// false: span is no power of two >= 1024, or a position or a bucket id does not fit an int
+bool span_geom(long n, int K, long span, SpanGeom* g) {
+  if (n <= 0 || n >= (1L << 31) || K <= 0 || K > 16384 || span < 1024 || (span & (span - 1))) return false;
+  if (span > (1L << 31)) span = 1L << 31;  // one span either way
+  long chunk = harp_bucket_chunk(n) < SPAN_CHUNK ? harp_bucket_chunk(n) : SPAN_CHUNK;
+  if (chunk > span) chunk = span;
+  const long cps = span / chunk;
+  const long seg = cps < SEG ? cps : SEG;
+  const long nch = (n + chunk - 1) / chunk;
+  const long nspans = (n + span - 1) / span;
+  if (nspans * K >= (1L << 30)) return false;
+  g->chunk = chunk;
+  g->nch = (int)nch;
+  g->cps = (int)cps;
+  g->seg = (int)seg;
+  g->nseg = (int)((nch + seg - 1) / seg);
+  g->sps = (int)(cps / seg);
+  g->nspans = (int)nspans;
+  g->nb = nspans * K;
+  return true;
+}
+
+}  // namespace
+
+// ints of workspace harp_bucket_labels_spans needs (0: arguments it rejects)
+HARP_EXPORT long harp_bucket_spans_workspace_ints(long n, int K, long span) {
+  SpanGeom g;
+  if (!span_geom(n, K, span, &g)) return 0;
+  // H[nch][K] + T[nseg][K] + counts[nb] + start[nb+1] + perm[n]
+  return (long)g.nch * K + (long)g.nseg * K + g.nb + (g.nb + 1) + n;
+}
+
+// Bucket labels (in [0, K)) span by span: perm[n] holds the point indices sorted by
+// (p / span, lab[p]) and start[nspans * K + 1] the offsets of the buckets q = s * K + g in
+// that order (monotone, start[last] = n), both inside the workspace at the offsets returned.
+// rank (optional, [n]) receives the inverse permutation. span: a power of two >= 1024. One
+// launch of each of the five kernels for all n.
+HARP_EXPORT int harp_bucket_labels_spans(const int* lab, long n, int K, long span, int* ws, long* start_off,
+                                         long* perm_off, int* rank, hipStream_t s) {
+  SpanGeom g;
+  if (!lab || !ws || !span_geom(n, K, span, &g)) return HARP_EBADARG;
+  int* H = ws;
+  int* T = H + (long)g.nch * K;
+  int* counts = T + (long)g.nseg * K;
+  int* start = counts + g.nb;
+  int* perm = start + g.nb + 1;
+  *start_off = start - ws;
+  *perm_off = perm - ws;
+  const size_t lds = (size_t)K * sizeof(int);
+  const unsigned kb = (unsigned)((K + 255) / 256);
+  label_hist_kernel<<<dim3(g.nch), dim3(256), lds, s>>>(lab, n, K, g.chunk, H);
+  colscan1_spans_kernel<<<dim3(g.nseg, kb), dim3(256), 0, s>>>(H, g.nch, K, g.seg, T);
+  colscan2_spans_kernel<<<dim3(g.nspans, kb), dim3(256), 0, s>>>(T, g.nseg, g.sps, K, counts);
+  segscan_kernel<<<dim3(1), dim3(1024), 0, s>>>(counts, (int)g.nb, start);
+  bucket_spans_kernel<<<dim3(g.nch), dim3(SPAN_TPB), lds, s>>>(lab, n, K, g.chunk, g.cps, g.seg, H, T, start, perm,
+                                                             rank);
   return harp_launch_status();
 }
 

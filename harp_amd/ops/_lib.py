@@ -37,6 +37,12 @@ _SIGNATURES = {
     "harp_kmeans_prepare": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "harp_uniform_rows_bf16": [c_void_p, c_long, c_int, c_int, c_float, c_float, c_ulonglong, c_long, c_int,
                                c_void_p],
+    # the span-ordered label sort of the K-means tail (csrc/segsum.hip; ops/segment.py)
+    "harp_bucket_spans_workspace_ints": [c_long, c_int, c_long],  # returns long
+    # lab, n, K, span, ws, &start_off, &perm_off, rank, stream
+    "harp_bucket_labels_spans": [c_void_p, c_long, c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    # labels, rank, rowof, n, stream
+    "harp_kmeans_finish_labels": [c_void_p, c_void_p, c_void_p, c_long, c_void_p],
 }
 
 

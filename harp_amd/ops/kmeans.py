@@ -41,12 +41,16 @@ ONES = 4  # X columns d..d+3 hold 1.0
 DEFAULT_VARIANT = 16
 KEYLESS_VARIANT, KEYED_VARIANT = 16, 15
 KEYLESS_MAX_DP = 128
-# The resolve pass scatters one 4-byte label per point. Run over all 1e8 points at once, the
-# label lines being written span 400 MB and every store goes to HBM as a partial line
-# (bucket + resolve 9.2 ms); over spans of points whose labels fit the memory-side cache the
-# stores merge there (7.55 ms at 4 or 16 spans; 64 spans pay launch gaps, 9.9 ms;
-# profiles/r7_keyless). Smaller inputs run as one span.
-RESOLVE_SPAN = 1 << 23
+# A span is an ordering of the tail's sort, not a launch: the points are bucketed by (index //
+# RESOLVE_SPAN, winning group) in one launch set, one resolve launch walks that permutation and
+# writes each point's row inside its group in sorted order, and one streaming pass gathers the
+# rows back into the labels (csrc/kmeans_resolve.hip). The span bounds that byte gather to
+# RESOLVE_SPAN bytes around the point's position; larger spans mean fewer, longer buckets.
+# Bucket + resolve + finish at N = 1e8, K = 1e4: 6.79 / 6.72 / 6.65 / 6.57 / 6.58 / 6.47 / 6.44 /
+# 6.32 ms at spans of 2^20 .. 2^27 (profiles/kmeans_tail_onepass): a span of rows (one byte per
+# point) that fits the memory-side cache needs no cutting, so 1e8 points are one span. Read at
+# call time; a power of two >= 1024.
+RESOLVE_SPAN = 1 << 27
 
 
 NARROW_MAX_DP = 256  # the register-resident assign kernel (X fragments live for the sweep)
@@ -269,11 +273,11 @@ def assign(X: torch.Tensor, op: CentroidOperand, sums: Optional[torch.Tensor] = 
                 continue
 
             def bucket_sum(lab, Xc):
-                if keyless:  # lab holds 32-row group ids: sort by group, resolve the row, sum
-                    for s0 in range(0, lab.numel(), RESOLVE_SPAN):
-                        ls, Xs = lab[s0:s0 + RESOLVE_SPAN], Xc[s0:s0 + RESOLVE_SPAN]
-                        perm, start = segment.bucket_labels(ls, swept_k(op) // 32)
-                        segment.resolve_rowsum(Xs, op.Cm2, perm, start, ls, sums)
+                if keyless:  # lab holds 32-row group ids: sort by (span, group), resolve the row, sum
+                    ng = swept_k(op) // 32
+                    perm, start, rank, rowof = segment.bucket_labels_spans(lab, ng, RESOLVE_SPAN, want_rank=True)
+                    segment.resolve_rowsum(Xc, op.Cm2, perm, start, rowof, sums, NG=ng)
+                    segment.finish_labels(lab, rank, rowof)
                 else:
                     perm, start = segment.bucket_labels(lab, op.Cm2.shape[0])
                     segment.bucket_rowsum(Xc, perm, start, sums)

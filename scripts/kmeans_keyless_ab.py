@@ -45,24 +45,20 @@ def main():
         return e
 
     def bucket_sum(v):
-        """[(before bucket, before sum, after sum)] per span: the keyless path works through the
-        points in spans of K.RESOLVE_SPAN (as ops.kmeans.assign does), the keyed path in one."""
+        """[(before bucket, before sum, after sum)]: the keyless path sorts by (span of
+        K.RESOLVE_SPAN points, group), resolves and finishes the labels (as ops.kmeans.assign does)."""
         sums[v].zero_()
-        marks = []
-        span = K.RESOLVE_SPAN if v == 16 else n
-        for s0 in range(0, n, span):
-            ls, Xs = lab[v][s0:s0 + span], X[s0:s0 + span]
-            e0 = ev()
-            if v == 15:
-                perm, start = segment.bucket_labels(ls, Kp)
-                e1 = ev()
-                segment.bucket_rowsum(Xs, perm, start, sums[v])
-            else:
-                perm, start = segment.bucket_labels(ls, ks // 32)
-                e1 = ev()
-                segment.resolve_rowsum(Xs, op.Cm2, perm, start, ls, sums[v])
-            marks.append((e0, e1, ev()))
-        return marks
+        e0 = ev()
+        if v == 15:
+            perm, start = segment.bucket_labels(lab[v], Kp)
+            e1 = ev()
+            segment.bucket_rowsum(X, perm, start, sums[v])
+        else:
+            perm, start, rank, rowof = segment.bucket_labels_spans(lab[v], ks // 32, K.RESOLVE_SPAN, want_rank=True)
+            e1 = ev()
+            segment.resolve_rowsum(X, op.Cm2, perm, start, rowof, sums[v], NG=ks // 32)
+            segment.finish_labels(lab[v], rank, rowof)
+        return [(e0, e1, ev())]
 
     times = {}
     for r in range(a.rounds + 1):  # round 0 warms up
