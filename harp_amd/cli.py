@@ -41,6 +41,11 @@ same parameters as named flags (which win when both are given):
             --test-dir --test-labels (csr)]
             algo kernel: the kernel function of the input against itself (daal_kernel_func
             matrixMatrix mode) -> kernel_values.csv  [--kernel linear|rbf --sigma --format]
+            algo quantile (alias qte): per-feature quantiles over the workers' row shards
+            (daal_quantile, QTEDaalCollectiveMapper) -> quantile_quantiles.csv, one row per q.
+            native (default): radix select, one histogram allreduce per pass, no row gather;
+            torch: sort of the gathered rows, at most 2**24 elements
+            [--q 0.1,0.5,0.9 --engine native|torch]
 
 ``maps`` = number of workers. Outside torchrun the CLI spawns ``maps`` local worker
 processes (RCCL on GPUs when ``maps`` <= visible GPUs, else gloo on CPU); under torchrun
@@ -99,7 +104,8 @@ EXTRA = {  # named-only flags
     "daal": [("k", int, 0), ("method", str, ""), ("label_cols", int, 1), ("n_trees", int, 50), ("max_depth", int, 10),
              ("engine", str, "native"), ("format", str, "dense"), ("labels", str, ""),
              ("min_support", float, 0.001), ("min_confidence", float, 0.7), ("rounds", int, 50), ("c", float, None),
-             ("kernel", str, "linear"), ("sigma", float, 1.0), ("test_dir", str, ""), ("test_labels", str, "")],
+             ("kernel", str, "linear"), ("sigma", float, 1.0), ("test_dir", str, ""), ("test_labels", str, ""),
+             ("q", str, "0.1,0.5,0.9")],
     "mds": [("work_dir", str, "harp-work/mds"), ("checkpoint_every", int, 0)],
 }
 
@@ -450,6 +456,14 @@ def _run_daal(comm, cfg):
         out = ST.low_order_moments(A, comm)
     elif algo == "pca":
         out = ST.pca(A, comm, cfg["method"] or "correlation")
+    elif algo in ("quantile", "qte"):
+        q = [float(v) for v in cfg["q"].split(",") if v.strip()]
+        d = _allmax(comm, A.shape[1])  # a worker without rows still takes part in every allreduce
+        if A.shape[0] == 0:
+            A = torch.zeros((0, d), dtype=torch.float64)
+        if cfg["engine"] == "native":
+            A = A.to(comm.device)
+        out = {"quantiles": ST.quantiles(A, q, comm, engine=cfg["engine"])}
     elif algo == "svd":
         out = ST.svd(A, comm)
     elif algo == "qr":

@@ -12,6 +12,8 @@ Each distributed algorithm is: local partial sums on the device (the Gram / cros
 partial is a GEMM — ``ops.linalg.gram``) -> one packed allreduce
 (:func:`~harp_amd.models.common.reduce_partials`) -> finalize on every worker in fp64.
 Inputs may be dense tensors or torch sparse (CSR/COO) tensors (the ``csr`` variants).
+Quantiles follow the same pattern with ``engine="native"``: per-worker integer digit histograms
+(``ops.quantile``), one allreduce per radix pass, the same pick on every worker.
 """
 from __future__ import annotations
 
@@ -424,11 +426,55 @@ def normalize_zscore(X: torch.Tensor, comm: Optional[Communicator] = None) -> to
 
 
 # ------------------------------------------------------------------ quantiles / sorting
-def quantiles(X: torch.Tensor, q=(0.1, 0.5, 0.9), comm: Optional[Communicator] = None) -> torch.Tensor:
-    """Per-feature quantiles [len(q), d] (daal_quantile). Distributed: exact, over the
-    all-gathered columns."""
+TORCH_QUANTILE_MAX = 1 << 24  # torch.quantile refuses a larger input
+
+
+def order_statistics(X: torch.Tensor, ranks, comm: Optional[Communicator] = None) -> torch.Tensor:
+    """Per-feature order statistics [len(ranks), d] in X's dtype (bf16 / fp32 / fp64): row i is
+    the element at global 0-based rank ``ranks[i]`` of every sorted column, over the rows of
+    all workers. Radix select (``ops.quantile.select``): nothing is sorted, gathered or widened;
+    the workers exchange one small integer histogram per pass."""
+    from ..ops import quantile as QT
+
+    return QT.select(X, ranks, comm)
+
+
+def quantiles(X: torch.Tensor, q=(0.1, 0.5, 0.9), comm: Optional[Communicator] = None,
+              engine: str = "torch") -> torch.Tensor:
+    """Per-feature quantiles [len(q), d] in fp64 (daal_quantile), linear interpolation between
+    the two neighbouring order statistics (``torch.quantile``'s rule, NaN columns included).
+
+    ``engine="torch"``: ``torch.quantile`` on the fp64 copy of the block, distributed over the
+    all-gathered rows; at most 2**24 elements. ``engine="native"``: the order statistics at
+    floor / ceil of ``q * (n_global - 1)`` by :func:`order_statistics` (any size, bf16 / fp32 /
+    fp64 input read in place, one histogram all-reduce per radix pass), then the same
+    interpolation on the [len(q), d] result: bit-equal to the torch engine."""
+    if engine == "native":
+        return _quantiles_native(X, q, comm)
+    if engine != "torch":
+        raise ValueError(f"engine={engine!r}: expected 'torch' or 'native'")
     Xa = gather_rows(_local(comm), X) if comm is not None else X
+    if Xa.numel() > TORCH_QUANTILE_MAX:
+        raise ValueError(f"the torch engine handles at most 2**24 elements (got {Xa.numel()}): "
+                         "use engine=\"native\"")
     return torch.quantile(Xa.double(), torch.tensor(q, dtype=torch.float64, device=Xa.device), dim=0)
+
+
+def _quantiles_native(X: torch.Tensor, q, comm: Optional[Communicator]) -> torch.Tensor:
+    qt = torch.as_tensor(q, dtype=torch.float64).reshape(-1)
+    if qt.numel() and not bool(((qt >= 0) & (qt <= 1)).all()):
+        raise ValueError("quantiles() q values must be in the range [0, 1]")
+    pos = {}
+
+    def ranks(n: int):  # torch.quantile's positions, in the same fp64 arithmetic
+        r = qt * (n - 1)
+        lo = r.floor()
+        pos["frac"] = r - lo
+        return torch.cat([lo, r.ceil()]).long()
+
+    v = order_statistics(X, ranks, comm).double()
+    k = qt.numel()
+    return torch.lerp(v[:k], v[k:], pos["frac"].to(v.device)[:, None])
 
 
 def sort_features(X: torch.Tensor) -> torch.Tensor:
