@@ -31,8 +31,19 @@
 
 #include <type_traits>
 
+// No FMA contraction in this file. The compiler's __dmul_rn / __dadd_rn are plain x * y and
+// x + y that carry the contract flag of their own header, so after inlining
+// __dadd_rn(__dmul_rn(ci, ki), __dmul_rn(cj, kj)) became fma(ci, ki, cj * kj): one rounding
+// fewer than the oracle's, gradients one ulp off and, on tied scores, another trajectory.
+// The helpers below are compiled under the pragma and stay a multiply and an add.
+#pragma clang fp contract(off)
+
 namespace {
 
+__device__ __forceinline__ double add_rn(double x, double y) { return x + y; }
+__device__ __forceinline__ double sub_rn(double x, double y) { return x - y; }
+__device__ __forceinline__ double mul_rn(double x, double y) { return x * y; }
+__device__ __forceinline__ double div_rn(double x, double y) { return x / y; }
 
 // Arg-reductions (ties to the lower index), the DPP wave / block reductions: wave.h.
 // (__shfl_xor compiles to ds_bpermute: six dependent LDS round trips per reduction,
@@ -166,11 +177,11 @@ __global__ __launch_bounds__(T) void smo_kernel(const double* __restrict__ Kfull
         const double mg = yp ? -G[k] : G[k];
         const bool low = (yp && g0) || (!yp && lc);
         if (low && mg < mval) {
-          const double bt = __dsub_rn(mval, mg);
+          const double bt = sub_rn(mval, mg);
           const double kdu = KDL ? s_kd[t] : kdt[u];
-          double at = __dsub_rn(__dadd_rn(kii, kdu), __dmul_rn(2.0, kit[u]));
+          double at = sub_rn(add_rn(kii, kdu), mul_rn(2.0, kit[u]));
           if (!(at > 0)) at = tau;
-          const double sc = -__ddiv_rn(__dmul_rn(bt, bt), at);
+          const double sc = -div_rn(mul_rn(bt, bt), at);
           if (arg_better<false>(sc, t, sv, sj)) {
             sv = sc;
             sj = t;
@@ -199,19 +210,19 @@ __global__ __launch_bounds__(T) void smo_kernel(const double* __restrict__ Kfull
       for (int q = 0; q < EPT; ++q)
         if (q == kj) gj = G[q];
       const bool yp = (ypos >> kj) & 1;
-      s_bc[2] = __dsub_rn(mval, yp ? -gj : gj);  // bt_j
+      s_bc[2] = sub_rn(mval, yp ? -gj : gj);  // bt_j
       s_bc[3] = sat;                               // at_j
       s_bc[4] = aj_pf;
       s_bc[5] = yp ? 1.0 : -1.0;
     }
     __syncthreads();
     const double btj = s_bc[2], atj = s_bc[3], aj = s_bc[4], yj = s_bc[5], ai = s_bc[6], yi = s_bc[7];
-    double delta = __ddiv_rn(btj, atj);
-    const double lim_i = yi > 0 ? __dsub_rn(C, ai) : ai;
-    const double lim_j = yj > 0 ? aj : __dsub_rn(C, aj);
+    double delta = div_rn(btj, atj);
+    const double lim_i = yi > 0 ? sub_rn(C, ai) : ai;
+    const double lim_j = yj > 0 ? aj : sub_rn(C, aj);
     delta = fmax(0.0, fmin(delta, fmin(lim_i, lim_j)));
-    const double dai = __dmul_rn(yi, delta), daj = -__dmul_rn(yj, delta);
-    const double nai = __dadd_rn(ai, dai), naj = __dadd_rn(aj, daj);
+    const double dai = mul_rn(yi, delta), daj = -mul_rn(yj, delta);
+    const double nai = add_rn(ai, dai), naj = add_rn(aj, daj);
     // owners refresh the box bits (i != j: j has mg < m = mg_i)
     if (tid == (i & (T - 1))) {
       const int k = i / T;
@@ -226,7 +237,7 @@ __global__ __launch_bounds__(T) void smo_kernel(const double* __restrict__ Kfull
       a[j] = naj;
     }
     // ---- G += y (yi dai K_i + yj daj K_j)
-    const double ci = __dmul_rn(yi, dai), cj = __dmul_rn(yj, daj);
+    const double ci = mul_rn(yi, dai), cj = mul_rn(yj, daj);
     const double* Kj = Kfull + (long)(IDENT ? j : ids[j]) * ldk;
     asm volatile("" : "+v"(tid));
 #pragma unroll
@@ -247,9 +258,9 @@ __global__ __launch_bounds__(T) void smo_kernel(const double* __restrict__ Kfull
         const int k = k0 + u;
         const int t = tid + T * k;
         if (k >= EPT || t >= n) continue;
-        const double v = __dadd_rn(__dmul_rn(ci, ki[u]), __dmul_rn(cj, kj[u]));
+        const double v = add_rn(mul_rn(ci, ki[u]), mul_rn(cj, kj[u]));
         const double yt = ((ypos >> k) & 1) ? 1.0 : -1.0;
-        G[k] = __dadd_rn(G[k], __dmul_rn(yt, v));
+        G[k] = add_rn(G[k], mul_rn(yt, v));
       }
     }
     __syncthreads();  // s_bc and the partial arrays are rewritten by the next step
@@ -454,10 +465,10 @@ __global__ __launch_bounds__(kCoopT) void smo_coop_kernel(const double* __restri
       const bool yp = (ypos >> k) & 1, lc = (ltC >> k) & 1, z0 = (gt0 >> k) & 1;
       const double mg = yp ? -G[k] : G[k];
       if (((yp && z0) || (!yp && lc)) && mg < mval) {
-        const double bt = __dsub_rn(mval, mg);
-        double at = __dsub_rn(__dadd_rn(kii, KD[k]), __dmul_rn(2.0, KI[k]));
+        const double bt = sub_rn(mval, mg);
+        double at = sub_rn(add_rn(kii, KD[k]), mul_rn(2.0, KI[k]));
         if (!(at > 0)) at = tau;
-        const double sc = -__ddiv_rn(__dmul_rn(bt, bt), at);
+        const double sc = -div_rn(mul_rn(bt, bt), at);
         if (arg_better<false>(sc, t, sv, sj)) {
           sv = sc;
           sj = t;
@@ -504,12 +515,12 @@ __global__ __launch_bounds__(kCoopT) void smo_coop_kernel(const double* __restri
     }
     if (j >= n) break;
     // ---- update (identical arithmetic in every thread), owners refresh alpha and box bits
-    double delta = __ddiv_rn(btj, atj);
-    const double lim_i = yi > 0 ? __dsub_rn(C, ai) : ai;
-    const double lim_j = yj > 0 ? aj : __dsub_rn(C, aj);
+    double delta = div_rn(btj, atj);
+    const double lim_i = yi > 0 ? sub_rn(C, ai) : ai;
+    const double lim_j = yj > 0 ? aj : sub_rn(C, aj);
     delta = fmax(0.0, fmin(delta, fmin(lim_i, lim_j)));
-    const double dai = __dmul_rn(yi, delta), daj = -__dmul_rn(yj, delta);
-    const double nai = __dadd_rn(ai, dai), naj = __dadd_rn(aj, daj);
+    const double dai = mul_rn(yi, delta), daj = -mul_rn(yj, delta);
+    const double nai = add_rn(ai, dai), naj = add_rn(aj, daj);
     if (i % S == g0) {
       const int k = i / S;
 #pragma unroll
@@ -526,7 +537,7 @@ __global__ __launch_bounds__(kCoopT) void smo_coop_kernel(const double* __restri
       ltC = naj < C ? ltC | (1u << k) : ltC & ~(1u << k);
       gt0 = naj > 0 ? gt0 | (1u << k) : gt0 & ~(1u << k);
     }
-    const double ci = __dmul_rn(yi, dai), cj = __dmul_rn(yj, daj);
+    const double ci = mul_rn(yi, dai), cj = mul_rn(yj, daj);
     const double* Kj = Kfull + (long)(IDENT ? j : ids[j]) * ldk;
     double KJ[EPT];
 #pragma unroll
@@ -536,9 +547,9 @@ __global__ __launch_bounds__(kCoopT) void smo_coop_kernel(const double* __restri
     }
 #pragma unroll
     for (int k = 0; k < EPT; ++k) {
-      const double v = __dadd_rn(__dmul_rn(ci, KI[k]), __dmul_rn(cj, KJ[k]));
+      const double v = add_rn(mul_rn(ci, KI[k]), mul_rn(cj, KJ[k]));
       const double yt = ((ypos >> k) & 1) ? 1.0 : -1.0;
-      G[k] = __dadd_rn(G[k], __dmul_rn(yt, v));
+      G[k] = add_rn(G[k], mul_rn(yt, v));
     }
   }
 #pragma unroll
@@ -596,11 +607,7 @@ HARP_EXPORT int harp_svm_smo(const double* K, long ldk, const int* ids, const lo
   if (e1 <= 8) SMO(8, 1024);
   if (e1 <= 16) SMO(16, 1024);
   if (e1 <= 24) SMO(24, 1024);
-  const int e2 = (max_n + 511) / 512;
-  if (e2 <= 32) SMO(32, 512);
-  if (e2 <= 40) SMO(40, 512);
-  if (e2 <= 48) SMO(48, 512);
-  SMO(64, 512);
+  SMO(64, 512);  // the only 512-thread tier: n > 24576 means ceil(n / 512) >= 49, past any smaller one
 #undef SMO
 }
 

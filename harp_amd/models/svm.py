@@ -210,8 +210,8 @@ class BinarySVM:
         G = -torch.ones(n, dtype=torch.float64, device=K.device)
         Cc, tau = self.C, self.tau
         pos = yv > 0
-        it = 0
-        for it in range(self.max_iter):
+        steps = 0  # updates performed (at the cap and at convergence alike, as on the device)
+        for _ in range(self.max_iter):
             mg = -yv * G
             up = (pos & (a < Cc)) | (~pos & (a > 0))
             low = (pos & (a > 0)) | (~pos & (a < Cc))
@@ -238,7 +238,8 @@ class BinarySVM:
             a[j] += daj
             # G += Q[:, i] dai + Q[:, j] daj,  Q = y y^T K
             G += yv * (yi * dai * K[i] + yj * daj * K[j])
-        return self._finish(Xd, yv, a, G, it)
+            steps += 1
+        return self._finish(Xd, yv, a, G, steps)
 
     def _finish(self, Xd, yv, a, G, steps: int, rows: Optional[torch.Tensor] = None) -> "BinarySVM":
         """Bias from the free SVs (or the violating-pair midpoint) and the SV set. ``rows``

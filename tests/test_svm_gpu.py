@@ -75,7 +75,10 @@ def test_coop_multiclass_matches_one_cu_kernel(cuda, n, classes, monkeypatch):
 
 
 def test_device_multiclass_large_machines(cuda):
-    """Machines past 8192 rows take the 1024 x 24 and 512-thread forms with LDS column lists."""
+    """Three machines of ~20000 rows with column lists: by default (at most 16 machines of
+    4096 rows or more) they run on the cooperative kernel, 16 CUs and two elements per
+    thread each. The one-workgroup 1024 x 24 and 512-thread forms are reached in
+    tests/test_svm_edges_gpu.py."""
     X, y = _data(30000, 8, 11, classes=3)
     Xg, yg = X.to(cuda), y.to(cuda)
     dev = MultiClassSVM(3, C=1.0, kernel="rbf", sigma=3.0).fit(Xg, yg)

@@ -32,6 +32,25 @@ def test_binary_svm_matches_libsvm(kernel):
     assert abs(m.coef.abs().sum().item() - float(abs(ref.dual_coef_).sum())) < 1e-3
 
 
+def test_oracle_n_iterations_counts_updates():
+    """``n_iterations`` of the PyTorch loop is updates + 1 at a step cap and at convergence
+    alike (the device kernel's count)."""
+    X, y = _blobs(120, 3)
+    for cap, want in ((0, 1), (1, 2), (5, 6)):
+        m = S.BinarySVM(C=1.0, max_iterations=cap, solver="torch").fit(X, y)
+        assert m.n_iterations == want, (cap, m.n_iterations)
+        assert int((m.alpha != 0).sum()) <= 2 * cap
+    # two mirrored points: one update (delta = 2 / 4) zeroes the gradient, the second pass stops
+    two = S.BinarySVM(C=1.0, solver="torch").fit(torch.tensor([[1.0], [-1.0]]), torch.tensor([1.0, -1.0]))
+    assert two.n_iterations == 2 and two.alpha.tolist() == [0.5, 0.5] and two.grad.tolist() == [0.0, 0.0]
+    # a converged run: a cap of exactly its updates, or any larger one, changes nothing
+    full = S.BinarySVM(C=1.0, solver="torch").fit(X, y)
+    assert 6 < full.n_iterations < 100000
+    for cap in (full.n_iterations - 1, full.n_iterations + 10):
+        m = S.BinarySVM(C=1.0, max_iterations=cap, solver="torch").fit(X, y)
+        assert m.n_iterations == full.n_iterations and torch.equal(m.alpha, full.alpha)
+
+
 def test_multiclass_svm():
     from sklearn.svm import SVC
 
