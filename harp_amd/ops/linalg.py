@@ -9,6 +9,7 @@ Sparse (CSR / COO) inputs go to ``ops.csr_stats`` in fp64: the native CSR kernel
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -129,6 +130,9 @@ class FeatureMajor:
         st = _kl.kernels().harp_uniform_rows_bf16(XT.data_ptr(), nb * d_pad, KT, KT, float(lo), float(hi),
                                                   seed & 0xFFFFFFFFFFFFFFFF, 0, 0, _lib.stream_ptr(XT.device))
         _lib.check(st, "uniform_rows")
+        # the generator draws in fp32 and rounds to bf16, which can land on hi itself (or below
+        # a lo that bf16 does not hold): keep the promised half-open interval
+        XT[:, :d].clamp_(min=_bf16_step(lo, up=True), max=_bf16_step(hi, up=False, strict=True))
         XT[:, d:].zero_()
         full, part = divmod(n, KT)  # whole sample blocks, samples in the partial block
         XT[:full, d] = 1.0
@@ -137,6 +141,20 @@ class FeatureMajor:
             XT[full, :, part:].zero_()
         XT[full + (1 if part else 0):].zero_()
         return cls(XT, n, d)
+
+
+def _bf16_step(x: float, up: bool, strict: bool = False) -> float:
+    """The nearest bf16 value >= x (``up``) or <= x, or < x with ``strict``."""
+    t = torch.tensor([x], dtype=torch.float32).to(torch.bfloat16)
+    v = float(t)
+    if (v < x if up else (v > x or (strict and v >= x))):
+        b = t.view(torch.int16)
+        if v == 0.0:
+            b.fill_(0x0001 if up else -0x7FFF)  # the smallest positive / negative bf16
+        else:
+            b += 1 if (v > 0) == up else -1
+        v = float(t)
+    return v
 
 
 SYRK_VARIANT = 0  # the one shipped kernel (profiles/r2_syrk: alternatives measured slower, removed)
@@ -211,11 +229,20 @@ def house_tsqr(A: torch.Tensor, want_q: bool = True):
     W = lib.harp_tsqr_width(d)
     if W < 0:
         raise ValueError(f"house_tsqr supports d <= {TSQR_MAX_D} (got {d})")
+    # The kernels form the column norm as sqrt(alpha^2 + sum of squares) unscaled, so entries
+    # beyond about 2^+-511 would square out of range. Factor A 2^-e with |A|_max 2^-e in
+    # [1/2, 1) and scale R back: a power of two, so every bit of Q and R is what it was for
+    # inputs that were in range before.
+    amax = float(A.abs().max()) if A.numel() else 0.0
+    if not math.isfinite(amax):
+        raise ValueError("house_tsqr: the matrix holds a non-finite entry")
+    e = math.frexp(amax)[1] if amax > 0.0 else 0
     TBR = lib.harp_tsqr_rows_per_block()
     dev = A.device
     st = _lib.stream_ptr(dev)
     M = torch.zeros((n, W), dtype=torch.float64, device=dev)
-    M[:, :d] = A
+    # in two factors: 2^-e alone overflows for a subnormal |A|_max
+    M[:, :d] = A if e == 0 else (A * 2.0 ** (-(e // 2))) * 2.0 ** (-(e - e // 2))
     levels = []
     while True:
         rows = M.shape[0]
@@ -233,6 +260,8 @@ def house_tsqr(A: torch.Tensor, want_q: bool = True):
     sgn = torch.sign(torch.diagonal(Rf)[:d])
     sgn[sgn == 0] = 1
     Rout = (Rf[:d, :d] * sgn[:, None]).contiguous()
+    if e != 0:
+        Rout = (Rout * 2.0 ** (e // 2)) * 2.0 ** (e - e // 2)
     if not want_q:
         return None, Rout
     S = None

@@ -3,6 +3,7 @@ import pytest
 import torch
 
 from harp_amd.ops import linalg as LA
+from tests.syrk_cases import bound_ratio
 
 pytestmark = pytest.mark.gpu
 
@@ -17,6 +18,10 @@ def test_gram_stats_matches_fp64(cuda, n, d):
     assert torch.allclose(s.double(), Xb.sum(0), rtol=1e-5, atol=1e-2)
     ref = Xb.t() @ Xb
     assert torch.allclose(G.double(), ref, rtol=2e-5, atol=1e-3 * ref.abs().max().item() * 1e-3 + 1e-2)
+    # ... and elementwise within the any-order summation bound (tests/syrk_cases.py), which
+    # scales with |X|^T |X| and has no absolute floor (sums and count included)
+    Gs = LA.symmetrize_upper(LA.syrk_t(fm))
+    assert bound_ratio(Gs, X, fm.ld) <= 1.0
 
 
 def test_feature_major_blocked_layout(cuda):
@@ -63,6 +68,7 @@ def test_syrk_variants_agree(cuda, variant, n, d):
     ref = Xb.t() @ Xb
     got = G[: d + 1, : d + 1].double()
     assert torch.allclose(got, ref, rtol=2e-5, atol=1e-2), (got - ref).abs().max()
+    assert bound_ratio(G, X, fm.ld) <= 1.0
 
 
 @pytest.mark.parametrize("n,d", [(1, 1), (300, 5), (4096, 16), (70000, 33), (200_000, 64), (64, 64)])
