@@ -46,6 +46,13 @@ same parameters as named flags (which win when both are given):
             native (default): radix select, one histogram allreduce per pass, no row gather;
             torch: sort of the gathered rows, at most 2**24 elements
             [--q 0.1,0.5,0.9 --engine native|torch]
+            algo outlier: outlier detection over the workers' row shards (daal_outlier
+            unidensebatch / multidensebatch / bacondensebatch) -> outlier_weights.csv, one weight
+            row per input row (1 = inlier; [n, d] for uni, [n] otherwise), the workers' rows in
+            rank order. native (default): ops/outlier.py, one pass per BACON iteration and one
+            record allreduce per pass, at most 64 features; torch: BACON needs maps = 1
+            [--method uni|multi|bacon --engine native|torch --alpha 0.05 (bacon)
+            --threshold (uni: 3.0, multi: chi2_0.999(d))]
 
 ``maps`` = number of workers. Outside torchrun the CLI spawns ``maps`` local worker
 processes (RCCL on GPUs when ``maps`` <= visible GPUs, else gloo on CPU); under torchrun
@@ -105,7 +112,7 @@ EXTRA = {  # named-only flags
              ("engine", str, "native"), ("format", str, "dense"), ("labels", str, ""),
              ("min_support", float, 0.001), ("min_confidence", float, 0.7), ("rounds", int, 50), ("c", float, None),
              ("kernel", str, "linear"), ("sigma", float, 1.0), ("test_dir", str, ""), ("test_labels", str, ""),
-             ("q", str, "0.1,0.5,0.9")],
+             ("q", str, "0.1,0.5,0.9"), ("alpha", float, 0.05), ("threshold", float, None)],
     "mds": [("work_dir", str, "harp-work/mds"), ("checkpoint_every", int, 0)],
 }
 
@@ -464,6 +471,8 @@ def _run_daal(comm, cfg):
         if cfg["engine"] == "native":
             A = A.to(comm.device)
         out = {"quantiles": ST.quantiles(A, q, comm, engine=cfg["engine"])}
+    elif algo == "outlier":
+        out = _run_daal_outlier(comm, cfg, A)
     elif algo == "svd":
         out = ST.svd(A, comm)
     elif algo == "qr":
@@ -502,6 +511,31 @@ def _run_daal(comm, cfg):
     else:
         raise ValueError(f"unknown daal algo {algo}")
     return _save_daal(comm, cfg, out)
+
+
+def _run_daal_outlier(comm, cfg, A):
+    """Outlier weights of the workers' row shards (daal_outlier). Every worker computes the
+    weights of its own rows; rank 0 writes them in rank order."""
+    from .models import stats as ST
+    from .parallel.partition_util import allgather_objects
+
+    method, engine = cfg["method"] or "bacon", cfg["engine"]
+    d = _allmax(comm, A.shape[1])  # a worker without rows still takes part in every allreduce
+    if A.shape[0] == 0:
+        A = torch.zeros((0, d), dtype=torch.float64)
+    if engine == "native":
+        A = A.to(comm.device)
+    if method == "uni":
+        thr = 3.0 if cfg["threshold"] is None else cfg["threshold"]
+        w = ST.outliers_univariate(A, thr, comm, engine=engine)
+    elif method == "multi":
+        w = ST.outliers_multivariate(A, cfg["threshold"], comm, engine=engine)
+    elif method == "bacon":
+        w = ST.outliers_bacon(A, alpha=cfg["alpha"], comm=comm, engine=engine)
+    else:
+        raise ValueError(f"method={method!r}: expected 'uni', 'multi' or 'bacon'")
+    parts = allgather_objects(comm, [w.cpu()]) if comm.world_size > 1 else [w.cpu()]
+    return {"weights": torch.cat(parts)}
 
 
 def _run_daal_boost(comm, cfg, A):

@@ -483,14 +483,29 @@ def sort_features(X: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------ outlier detection
+def _check_engine(engine: str, X: torch.Tensor) -> bool:
+    """True for the native engine (``ops.outlier``: HIP kernels on the device, their fp64 torch
+    mirror on the CPU), after checking its width limit."""
+    if engine == "torch":
+        return False
+    if engine != "native":
+        raise ValueError(f"engine={engine!r}: expected 'torch' or 'native'")
+    from ..ops import outlier as OL
+
+    OL.check_width(X.shape[1])
+    return True
+
+
 def outliers_univariate(X: torch.Tensor, threshold: float = 3.0, comm: Optional[Communicator] = None,
                         init: str = "moments", location: Optional[torch.Tensor] = None,
-                        scatter: Optional[torch.Tensor] = None) -> torch.Tensor:
+                        scatter: Optional[torch.Tensor] = None, engine: str = "torch") -> torch.Tensor:
     """Per-feature weights (1 = inlier): |x - location| / scatter <= threshold.
     ``init``: "moments" (global mean / standard deviation), "default" (DAAL
     univariate_outlier_detection's default initialisation: location 0, scatter 1 -- the
     reference app, daal_outlier/unidensebatch, runs it), or "given" (``location`` /
-    ``scatter`` per feature)."""
+    ``scatter`` per feature). ``engine="native"``: one pass over X in its own dtype
+    (``ops.outlier.univariate``), no fp64 copy, the same weights on every element."""
+    native = _check_engine(engine, X)
     if init == "moments":
         mom = low_order_moments(X, comm)
         loc, sc = mom["mean"].to(X.device), mom["standardDeviation"].to(X.device)
@@ -501,6 +516,10 @@ def outliers_univariate(X: torch.Tensor, threshold: float = 3.0, comm: Optional[
         loc, sc = location.double().to(X.device), scatter.double().to(X.device)
     else:
         raise ValueError(init)
+    if native:
+        from ..ops import outlier as OL
+
+        return OL.univariate(X, loc, sc, threshold)
     z = (X.double() - loc) / sc.clamp_min(1e-300)
     return (z.abs() <= threshold).to(X.dtype)
 
@@ -512,24 +531,50 @@ def mahalanobis_sq(X: torch.Tensor, mean: torch.Tensor, cov: torch.Tensor) -> to
 
 
 def outliers_multivariate(X: torch.Tensor, threshold: Optional[float] = None,
-                          comm: Optional[Communicator] = None) -> torch.Tensor:
+                          comm: Optional[Communicator] = None, engine: str = "torch") -> torch.Tensor:
     """Row weights (1 = inlier) by Mahalanobis distance to the global mean/covariance;
-    default threshold = chi2_{0.999}(d) on the squared distance."""
+    default threshold = chi2_{0.999}(d) on the squared distance. ``engine="native"``: the same
+    covariance, then one ``ops.outlier.mahalanobis_pass`` that writes the weights (no [n, d]
+    temporary; at most 64 features)."""
+    native = _check_engine(engine, X)
     r = covariance(X, comm)
-    d2 = mahalanobis_sq(X, r["mean"].to(X.device), r["covariance"].to(X.device))
     if threshold is None:
         from scipy.stats import chi2
 
         threshold = float(chi2.ppf(0.999, X.shape[1]))
+    if native:
+        from ..ops import outlier as OL
+
+        mean = r["mean"].to(X.device)
+        mask = torch.zeros(X.shape[0], dtype=torch.uint8, device=X.device)
+        OL.mahalanobis_pass(X, mean, OL.whiten(r["covariance"].to(X.device)), threshold, mean, mask=mask,
+                            strict=False, want_stats=False)
+        return mask.to(X.dtype)
+    d2 = mahalanobis_sq(X, r["mean"].to(X.device), r["covariance"].to(X.device))
     return (d2 <= threshold).to(X.dtype)
 
 
-def outliers_bacon(X: torch.Tensor, alpha: float = 0.05, init: str = "median", max_iter: int = 100) -> torch.Tensor:
-    """BACON outlier detection (Billor, Hadi & Velleman 2000; daal bacon_outlier_detection):
-    grow a clean basic subset by Mahalanobis distance until it stabilises; returns row
-    weights (1 = inlier)."""
+def _bacon_threshold(n: int, p: int, r: int, alpha: float) -> float:
     from scipy.stats import chi2
 
+    h = (n + p + 1) // 2
+    c = max(0.0, (h - r) / (h + r)) + 1 + (p + 1) / max(n - p, 1) + 1 / max(n - h - p, 1)
+    return c * math.sqrt(chi2.ppf(1 - alpha / n, p))
+
+
+def outliers_bacon(X: torch.Tensor, alpha: float = 0.05, init: str = "median", max_iter: int = 100,
+                   comm: Optional[Communicator] = None, engine: str = "torch") -> torch.Tensor:
+    """BACON outlier detection (Billor, Hadi & Velleman 2000; daal bacon_outlier_detection):
+    grow a clean basic subset by Mahalanobis distance until it stabilises; returns row
+    weights (1 = inlier).
+
+    ``engine="torch"`` works on one worker's rows (it raises when ``comm`` has more). With
+    ``engine="native"`` every worker passes its own rows (an empty shard is legal) and gets the
+    weights of those rows; see :func:`bacon_native`."""
+    if _check_engine(engine, X):
+        return bacon_native(X, alpha, init, max_iter, comm)["weights"]
+    if comm is not None and comm.world_size > 1:
+        raise ValueError('the torch BACON engine runs on one worker\'s rows: use engine="native"')
     Xd = X.double()
     n, p = Xd.shape
     if init == "median":
@@ -539,18 +584,91 @@ def outliers_bacon(X: torch.Tensor, alpha: float = 0.05, init: str = "median", m
     m = min(n, max(4 * p, p + 1))
     basic = torch.zeros(n, dtype=torch.bool, device=X.device)
     basic[torch.argsort(d0)[:m]] = True
-    cnp = lambda r: max(0.0, 1 + (p + 1) / (n - p) + 2 / (n - 1 - 3 * p) if n - 1 - 3 * p > 0 else 1.0)  # noqa: E731
     for _ in range(max_iter):
         sub = Xd[basic]
         mu = sub.mean(0)
         cov = torch.cov(sub.t()).reshape(p, p)
         dist = mahalanobis_sq(Xd, mu, cov).clamp_min(0).sqrt()
-        r = int(basic.sum())
-        h = (n + p + 1) // 2
-        c = max(0.0, (h - r) / (h + r)) + 1 + (p + 1) / max(n - p, 1) + 1 / max(n - h - p, 1)
-        thr = c * math.sqrt(chi2.ppf(1 - alpha / n, p))
+        thr = _bacon_threshold(n, p, int(basic.sum()), alpha)
         new = dist < thr
         if torch.equal(new, basic):
             break
         basic = new
     return basic.to(X.dtype)
+
+
+def bacon_native(X: torch.Tensor, alpha: float = 0.05, init: str = "median", max_iter: int = 100,
+                 comm: Optional[Communicator] = None, trace: Optional[list] = None) -> Dict[str, object]:
+    """BACON on ``ops.outlier.mahalanobis_pass``: one pass over X (in its own dtype, in place) per
+    iteration, which yields the distances under the current model, the new membership, the number
+    of rows that changed sides and the shifted sums and scatter of the new members; the next model
+    follows from those. Thresholds, subset size ``m = min(n, max(4p, p + 1))`` and stopping rule
+    are the torch engine's. At most 64 features.
+
+    1. ``init="median"``: lower medians by radix select at rank ``(n - 1) // 2`` (what
+       ``torch.median`` returns), one Euclidean pass for the squared distances; otherwise the
+       all-rows mean and covariance and one Mahalanobis pass.
+    2. The m-th smallest squared distance by radix select on the [n, 1] distance block; the initial
+       subset is every row at or below it. That is ``argsort(d0)[:m]`` whenever the m-th and
+       (m + 1)-th distances differ; with a tie at that rank every tied row joins (an argsort
+       would take them in an unspecified order).
+    3. One pass for the initial subset's statistics.
+    4. Per iteration: the model from the record (on the device), one pass, one read of ``(count,
+       changed)`` by the host; stop at ``changed == 0`` or ``max_iter``. A comparison of squared
+       distances to the squared threshold replaces the torch engine's square root.
+
+    With ``comm`` each worker holds its own rows: the selects sum integer histograms, every pass
+    of steps 3 and 4 is followed by one ``all_reduce`` of the record, and no rows move. Peak extra
+    device memory: the mask (n bytes), the initial distances (8 n bytes, freed after step 2) and
+    the block partials; no [n, d] temporary.
+
+    Returns ``weights`` [n_local] in X's dtype, ``iterations`` (passes of step 4) and ``n``.
+    ``trace`` (a list) receives per pass ``(center, P, t2, strict)``, for tests that check how
+    far the rows lie from each threshold."""
+    from ..ops import outlier as OL
+    from ..ops import quantile as QT
+
+    p = X.shape[1]
+    OL.check_width(p)
+    dev = X.device
+    seen: Dict[str, int] = {}
+
+    def lower_median(n: int):
+        seen["n"] = n
+        return [(n - 1) // 2]
+
+    if init == "median":
+        center = QT.select(X, lower_median, comm)[0].double()
+        P0 = None
+        n = seen["n"]
+    else:
+        red = reduce_partials(_local(comm), covariance_partial(X), dtype=torch.float64)
+        n = int(red["n"].item())
+        fin = covariance_finalize(red)
+        center = fin["mean"].to(dev)
+        P0 = OL.whiten(fin["covariance"].to(dev))
+    m = min(n, max(4 * p, p + 1))
+    d0 = OL.mahalanobis_pass(X, center, P0, math.inf, center, want_dist=True, strict=False,
+                             want_stats=False)["dist2"]
+    t0 = float(QT.select(d0[:, None], [m - 1], comm)[0, 0])
+    del d0
+    if trace is not None:
+        trace.append((center, P0, t0, False))
+    mask = torch.zeros(X.shape[0], dtype=torch.uint8, device=dev)
+    rec = OL.reduce_record(OL.mahalanobis_pass(X, center, P0, t0, center, mask=mask, strict=False)["record"], comm)
+    r = int(OL.split_record(rec, p)["count"])
+    shift = center
+    iterations = 0
+    for _ in range(max_iter):
+        mean, cov = OL.model_from_stats(rec, shift)
+        P = OL.whiten(cov)
+        t2 = _bacon_threshold(n, p, r, alpha) ** 2
+        if trace is not None:
+            trace.append((mean, P, t2, True))
+        rec = OL.reduce_record(OL.mahalanobis_pass(X, mean, P, t2, mean, mask=mask, strict=True)["record"], comm)
+        shift = mean
+        iterations += 1
+        r, changed = (int(v) for v in rec[:2].view(torch.int64).tolist())
+        if changed == 0:
+            break
+    return {"weights": mask.to(X.dtype), "iterations": iterations, "n": n}
