@@ -53,6 +53,11 @@ same parameters as named flags (which win when both are given):
             record allreduce per pass, at most 64 features; torch: BACON needs maps = 1
             [--method uni|multi|bacon --engine native|torch --alpha 0.05 (bacon)
             --threshold (uni: 3.0, multi: chi2_0.999(d))]
+            algo pqr (alias pivoted_qr): QR with column pivoting over the workers' row shards
+            (daal_pivoted_qr, PQRDaalCollectiveMapper) -> pqr_Q.csv (the workers' rows in rank
+            order), pqr_R.csv, pqr_permutation.csv. native (default): Householder TSQR and the
+            d x d pivoted QR of ops/pqr.py, at most 128 columns; host: LAPACK, maps = 1
+            [--engine native|host]
 
 ``maps`` = number of workers. Outside torchrun the CLI spawns ``maps`` local worker
 processes (RCCL on GPUs when ``maps`` <= visible GPUs, else gloo on CPU); under torchrun
@@ -473,6 +478,9 @@ def _run_daal(comm, cfg):
         out = {"quantiles": ST.quantiles(A, q, comm, engine=cfg["engine"])}
     elif algo == "outlier":
         out = _run_daal_outlier(comm, cfg, A)
+    elif algo in ("pqr", "pivoted_qr"):
+        cfg = dict(cfg, algo="pqr")  # the alias writes the same file names
+        out = _run_daal_pqr(comm, cfg, A)
     elif algo == "svd":
         out = ST.svd(A, comm)
     elif algo == "qr":
@@ -536,6 +544,23 @@ def _run_daal_outlier(comm, cfg, A):
         raise ValueError(f"method={method!r}: expected 'uni', 'multi' or 'bacon'")
     parts = allgather_objects(comm, [w.cpu()]) if comm.world_size > 1 else [w.cpu()]
     return {"weights": torch.cat(parts)}
+
+
+def _run_daal_pqr(comm, cfg, A):
+    """Column-pivoted QR of the workers' row shards (daal_pivoted_qr). Rank 0 writes R, the
+    permutation and Q, the workers' rows in rank order. The host engine needs maps = 1."""
+    from .models import stats as ST
+    from .parallel.partition_util import allgather_objects
+
+    if cfg["engine"] != "native":
+        return ST.pivoted_qr(A, comm if comm.world_size > 1 else None, engine=cfg["engine"])
+    d = _allmax(comm, A.shape[1])  # a worker without rows still takes part in the all-gather
+    if A.shape[0] == 0:
+        A = torch.zeros((0, d), dtype=torch.float64)
+    out = ST.pivoted_qr(A.to(comm.device), comm, engine="native")
+    if comm.world_size > 1:
+        out["Q"] = torch.cat(allgather_objects(comm, [out["Q"].cpu()]))
+    return out
 
 
 def _run_daal_boost(comm, cfg, A):

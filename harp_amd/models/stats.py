@@ -401,12 +401,49 @@ def cholesky(A: torch.Tensor) -> torch.Tensor:
     return torch.linalg.cholesky(A.double())
 
 
-def pivoted_qr(X: torch.Tensor) -> Dict[str, torch.Tensor]:
-    """QR with column pivoting (daal_pivoted_qr, batch): X[:, perm] = Q R."""
-    import scipy.linalg
+def pivoted_qr(X: torch.Tensor, comm: Optional[Communicator] = None, engine: str = "host") -> Dict[str, torch.Tensor]:
+    """QR with column pivoting (daal_pivoted_qr): X[:, perm] = Q R.
 
-    Q, R, piv = scipy.linalg.qr(X.double().cpu().numpy(), mode="economic", pivoting=True)
-    return {"Q": torch.from_numpy(Q), "R": torch.from_numpy(R), "permutation": torch.from_numpy(piv)}
+    ``engine="host"`` (batch only): LAPACK on the host, CPU tensors. ``engine="native"``: X =
+    Q1 R1 by Householder TSQR over the workers' row shards (never CholeskyQR2: rank-deficient
+    input is the use case), then the pivoted QR of the d x d factor, R1[:, perm] = Q2 R, on
+    every worker (``ops.pqr``: a HIP kernel on the GPU, its torch mirror on the CPU) and Q =
+    Q1 Q2. At most ``ops.pqr.MAX_D`` columns and at least as many rows as columns overall.
+    Returns Q (this worker's rows), R and permutation (int64) on X's device."""
+    if engine == "host":
+        if comm is not None:
+            raise ValueError("pivoted_qr: engine=\"host\" is batch only; use engine=\"native\" with a comm")
+        import scipy.linalg
+
+        Q, R, piv = scipy.linalg.qr(X.double().cpu().numpy(), mode="economic", pivoting=True)
+        return {"Q": torch.from_numpy(Q), "R": torch.from_numpy(R), "permutation": torch.from_numpy(piv)}
+    if engine != "native":
+        raise ValueError(f"engine={engine!r}: expected 'host' or 'native'")
+    from ..ops import pqr as PQ
+
+    comm = _local(comm)
+    n, d = X.shape
+    PQ.check_width(d)
+    n_global = n if comm.world_size == 1 else int(comm.all_gather_ints([n]).sum())
+    if n_global < d:
+        raise ValueError(f"pivoted_qr: the native engine needs at least as many rows as columns (got {n_global} x {d}): "
+                         "use engine=\"host\"")
+    Xd = X.double().contiguous()
+    if comm.world_size == 1 and _native_tsqr(Xd):
+        # Q2 seeds the top level of the explicit-Q pass: Q = Q1 Q2 without a GEMM over the rows
+        fac = {}
+
+        def seed(R1):
+            fac["Q2"], fac["R"], fac["perm"] = PQ.qrcp_small(R1)
+            return fac["Q2"]
+
+        Q, _ = LA.house_tsqr(Xd, True, seed=seed)
+        return {"Q": Q, "R": fac["R"], "permutation": fac["perm"].long()}
+    if n < d:  # the local QR of step 1 wants a full d x d factor: zero rows change nothing
+        Xd = torch.cat([Xd, Xd.new_zeros((d - n, d))])
+    qr = tsqr(Xd, comm, method="householder")
+    Q2, R, perm = PQ.qrcp_small(qr["R"].to(Xd.device).contiguous())
+    return {"Q": (qr["Q"] @ Q2)[:n], "R": R, "permutation": perm.long()}
 
 
 # ------------------------------------------------------------------ normalization

@@ -218,12 +218,16 @@ _lib.register({
 TSQR_MAX_D = 64
 
 
-def house_tsqr(A: torch.Tensor, want_q: bool = True):
+def house_tsqr(A: torch.Tensor, want_q: bool = True, seed=None):
     """Householder TSQR of a tall-skinny fp64 GPU matrix (d <= 64) on the native panel
     kernels: every 256-row block is factored by one workgroup (row per thread, registers),
     the stacked R's are factored level by level until one block remains, and the explicit Q
     is built top-down by applying each block's reflectors to its slice of the level above's
-    Q. Returns (Q [n, d] or None, R [d, d]) with R's diagonal made non-negative."""
+    Q. Returns (Q [n, d] or None, R [d, d]) with R's diagonal made non-negative.
+
+    ``seed``: a function of the finished R that returns a [d, d] matrix S; the top level of the
+    explicit-Q pass then starts from S instead of I, so the Q returned is Q S, at no GEMM over
+    the rows (``stats.pivoted_qr`` passes the Q factor of R's pivoted QR)."""
     n, d = A.shape
     lib = _lib.kernels()
     W = lib.harp_tsqr_width(d)
@@ -265,6 +269,11 @@ def house_tsqr(A: torch.Tensor, want_q: bool = True):
     if not want_q:
         return None, Rout
     S = None
+    if seed is not None:
+        # Q S = (Q_raw diag(sgn)) S: the sign flip moves onto the seed's rows
+        S = torch.zeros((W, W), dtype=torch.float64, device=dev)
+        S[:d, :d] = sgn[:, None] * seed(Rout)
+        sgn = torch.ones_like(sgn)
     for V, tau, rows in reversed(levels):
         Q = torch.empty((rows, W), dtype=torch.float64, device=dev)
         _lib.check(lib.harp_tsqr_apply(V.data_ptr(), W, rows, W, tau.data_ptr(), _lib.ptr(S), Q.data_ptr(), W, st),
