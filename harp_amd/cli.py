@@ -53,6 +53,12 @@ same parameters as named flags (which win when both are given):
             record allreduce per pass, at most 64 features; torch: BACON needs maps = 1
             [--method uni|multi|bacon --engine native|torch --alpha 0.05 (bacon)
             --threshold (uni: 3.0, multi: chi2_0.999(d))]
+            algo kmeans: fp64 Lloyd iterations over the workers' row shards (daal_kmeans) ->
+            kmeans_centroids.csv, kmeans_labels.csv. torch (default): [n, K] distance tensors;
+            native: ops/kmeans_f64.py, fp64 MFMA assign and one sorted pass for the sums, no
+            [n, K] tensor, at most 256 columns and 16384 centroids (dense input; CSR input
+            always takes csrc/kmeans_csr.hip on a GPU)  [--k 10 --method first|random|plusplus
+            --engine torch|native]
             algo pqr (alias pivoted_qr): QR with column pivoting over the workers' row shards
             (daal_pivoted_qr, PQRDaalCollectiveMapper) -> pqr_Q.csv (the workers' rows in rank
             order), pqr_R.csv, pqr_permutation.csv. native (default): Householder TSQR and the
@@ -138,6 +144,7 @@ def parse(app: str, argv: Sequence[str]) -> Dict[str, Any]:
     for (name, typ, _), val in zip(SPECS[app], a.positional):
         cfg[name] = typ(val)
     cfg["extra_args"] = list(a.positional[len(SPECS[app]):]) + extra
+    cfg["named"] = [name for name, _, _ in spec if getattr(a, name) is not None]  # flags given by name
     for name, _, _ in spec:
         v = getattr(a, name)
         if v is not None:
@@ -495,7 +502,11 @@ def _run_daal(comm, cfg):
         from .models.kmeans_csr import kmeans_init, kmeans_sparse
 
         C0 = kmeans_init(A, cfg["k"] or 10, comm, method=cfg["method"] or "first")
-        out = kmeans_sparse(A, C0, cfg["iterations"], comm)
+        # the native engine is opt-in here: without --engine the run stays on the torch engine
+        engine = cfg["engine"] if "engine" in cfg["named"] else "torch"
+        if engine == "native":  # the fp64 step of ops/kmeans_f64.py, on the worker's device
+            A = A.to(comm.device)
+        out = kmeans_sparse(A, C0, cfg["iterations"], comm, engine=engine)
     elif algo in ("dforest", "dforest_reg"):
         # one forest over the workers' row shards (last column = label / target); rank 0
         # writes the packed trees: nodes = (tree, feature, threshold, left), values [N, C]

@@ -88,11 +88,29 @@ def kmeans_init(X, K: int, comm: Optional[Communicator] = None, method: str = "f
     return C
 
 
-def kmeans_sparse(X, C0: torch.Tensor, iterations: int = 10, comm: Optional[Communicator] = None) -> Dict:
+def kmeans_sparse(X, C0: torch.Tensor, iterations: int = 10, comm: Optional[Communicator] = None,
+                  engine: str = "torch") -> Dict:
+    """Lloyd iterations in fp64 on a sparse or dense block. ``engine="native"`` runs a dense block
+    through the fp64 step of ``ops/kmeans_f64.py`` (HIP kernels on a GPU, no [n, K] tensor; the
+    torch formula on the CPU); sparse blocks take the same path under either engine."""
+    if engine not in ("torch", "native"):
+        raise ValueError(f"kmeans_sparse: engine is \"torch\" or \"native\" (got {engine!r})")
     comm = comm or Communicator()
     C = C0.to(device=X.device, dtype=torch.float64, copy=True)
     K, d = C.shape
     obj = []
+    if engine == "native" and not _is_sparse(X):
+        from ..ops import kmeans_f64 as KF
+
+        KF.check_width(d)
+        for _ in range(iterations):
+            lab, S, cnt, wss = KF.assign_accumulate(X, C)
+            r = reduce_partials(comm, {"S": S, "n": cnt, "o": wss.sum().reshape(1)})
+            cnt = r["n"].to(C.device)
+            nz = cnt > 0
+            C[nz] = r["S"].to(C.device)[nz] / cnt[nz, None]
+            obj.append(float(r["o"][0]))
+        return {"centroids": C, "objective": obj, "labels": lab.long()}
     if _is_sparse(X) and X.device.type == "cuda":
         # fused HIP E-step + accumulate (csrc/kmeans_csr.hip): no [n, K] tensors
         from ..ops import kmeans_csr as KC

@@ -33,6 +33,9 @@ ARCH = os.environ.get("HARP_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
              "-Wno-unused-result", "-I" + CSRC]
+# per source: flags on top of HIP_FLAGS (kmeans_f64 converts fp32 rows in registers and keeps the
+# compiler from pairing those operations into packed fp32 instructions)
+HIP_FILE_FLAGS = {"kmeans_f64.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 CXX = os.environ.get("CXX", "g++")
 CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-I" + CSRC]
 
@@ -63,7 +66,7 @@ def build_kernels(force: bool = False, jobs: int = 8, verbose: bool = False) -> 
         o = os.path.join(OBJ, os.path.basename(s) + ".o")
         objs.append(o)
         if force or _stale(o, [s] + headers):
-            todo.append([HIPCC] + HIP_FLAGS + ["-c", s, "-o", o])
+            todo.append([HIPCC] + HIP_FLAGS + HIP_FILE_FLAGS.get(os.path.basename(s), []) + ["-c", s, "-o", o])
     if todo:
         with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
             for fut in [ex.submit(_run, c) for c in todo]:
