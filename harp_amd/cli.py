@@ -64,6 +64,17 @@ same parameters as named flags (which win when both are given):
             order), pqr_R.csv, pqr_permutation.csv. native (default): Householder TSQR and the
             d x d pivoted QR of ops/pqr.py, at most 128 columns; host: LAPACK, maps = 1
             [--engine native|host]
+            algo optim: the optimization solvers over the workers' row shards
+            (daal_optimization_solvers; last column = target) -> optim_minimum.csv (intercept
+            first), optim_nIterations.csv. torch (default): models/optim.py expressions; native:
+            ops/glm.py, one fused pass per gradient and, for sgd / minibatch / momentum / adagrad
+            on one worker's GPU, the whole run in one launch (at most 256 features). Iterations,
+            batch size and learning rate default to the reference mapper's of the solver
+            [--solver sgd|minibatch|momentum|adagrad|lbfgs --objective mse|logistic
+            --engine torch|native --iterations --batch-size --learning-rate
+            --accuracy-threshold 1e-7 --step-length (lbfgs) --momentum 0.9 --seed 0 --point x0,..]
+            algo mse: value and gradient of the MSE objective at --point (default zeros;
+            MSEDenseBatch) -> mse_value.csv, mse_gradient.csv, both also printed
 
 ``maps`` = number of workers. Outside torchrun the CLI spawns ``maps`` local worker
 processes (RCCL on GPUs when ``maps`` <= visible GPUs, else gloo on CPU); under torchrun
@@ -123,7 +134,10 @@ EXTRA = {  # named-only flags
              ("engine", str, "native"), ("format", str, "dense"), ("labels", str, ""),
              ("min_support", float, 0.001), ("min_confidence", float, 0.7), ("rounds", int, 50), ("c", float, None),
              ("kernel", str, "linear"), ("sigma", float, 1.0), ("test_dir", str, ""), ("test_labels", str, ""),
-             ("q", str, "0.1,0.5,0.9"), ("alpha", float, 0.05), ("threshold", float, None)],
+             ("q", str, "0.1,0.5,0.9"), ("alpha", float, 0.05), ("threshold", float, None),
+             ("solver", str, "sgd"), ("objective", str, "mse"), ("batch_size", int, None),
+             ("learning_rate", float, None), ("accuracy_threshold", float, None), ("step_length", float, 1e-4),
+             ("momentum", float, 0.9), ("seed", int, 0), ("point", str, "")],
     "mds": [("work_dir", str, "harp-work/mds"), ("checkpoint_every", int, 0)],
 }
 
@@ -527,6 +541,8 @@ def _run_daal(comm, cfg):
                "values": torch.cat([t.value for t in forest.trees]), "n_trees": len(forest.trees)}
     elif algo in ("adaboost", "logitboost", "brownboost", "stump"):
         out = _run_daal_boost(comm, cfg, A)
+    elif algo in ("optim", "mse"):
+        out = _run_daal_optim(comm, cfg, A)
     else:
         raise ValueError(f"unknown daal algo {algo}")
     return _save_daal(comm, cfg, out)
@@ -555,6 +571,58 @@ def _run_daal_outlier(comm, cfg, A):
         raise ValueError(f"method={method!r}: expected 'uni', 'multi' or 'bacon'")
     parts = allgather_objects(comm, [w.cpu()]) if comm.world_size > 1 else [w.cpu()]
     return {"weights": torch.cat(parts)}
+
+
+# solver -> (iterations, batch size, learning rate): the defaults of the reference's mappers
+# (SGDDaal, SGDMINIDaal, SGDMOMOptDaal, ADAGDDaal, LBFGSDaal CollectiveMapper)
+_OPTIM_DEFAULTS = {"sgd": (1000, 1, 1.0), "minibatch": (1000, 4, 0.5), "momentum": (400, 4, 0.5),
+                   "adagrad": (1000, 1, 1.0), "lbfgs": (1000, None, None)}
+
+
+def _run_daal_optim(comm, cfg, A):
+    """The optimization solvers over the workers' row shards (daal_optimization_solvers; the last
+    column is the target). ``optim`` minimises the objective and returns ``minimum`` and
+    ``nIterations``; ``mse`` evaluates the MSE objective at ``--point`` (MSEDenseBatch)."""
+    from .models import optim as OP
+
+    algo, solver = cfg["algo"], cfg["solver"]
+    engine = cfg["engine"] if "engine" in cfg["named"] else "torch"  # the native engine is opt-in
+    d = _allmax(comm, A.shape[1])  # a worker without rows still takes part in every allreduce
+    if A.shape[0] == 0:
+        A = torch.zeros((0, d), dtype=torch.float64)
+    if engine == "native":
+        A = A.to(comm.device)
+    kinds = {"mse": OP.MSE, "logistic": OP.LogisticLoss}
+    objective = "mse" if algo == "mse" else cfg["objective"]
+    if objective not in kinds:
+        raise ValueError(f"objective={objective!r}: expected 'mse' or 'logistic'")
+    obj = kinds[objective](A[:, :-1], A[:, -1], comm if comm.world_size > 1 else None, engine=engine)
+    x0 = None
+    if cfg["point"]:
+        x0 = torch.tensor([float(v) for v in cfg["point"].split(",") if v.strip()], dtype=torch.float64)
+        if x0.numel() != obj.dim:
+            raise ValueError(f"--point has {x0.numel()} entries, the argument {obj.dim} (intercept first)")
+    if algo == "mse":
+        x = (torch.zeros(obj.dim, dtype=torch.float64) if x0 is None else x0).to(A.device)
+        v, g = obj.value_grad(x)
+        return {"value": v.reshape(1), "gradient": g, "point_value": float(v), "point_gradient": g.tolist()}
+    if solver not in _OPTIM_DEFAULTS:
+        raise ValueError(f"solver={solver!r}: expected one of {sorted(_OPTIM_DEFAULTS)}")
+    its, batch, lr = _OPTIM_DEFAULTS[solver]
+    its = cfg["iterations"] if "iterations" in cfg["named"] else its
+    batch = batch if cfg["batch_size"] is None else cfg["batch_size"]
+    lr = lr if cfg["learning_rate"] is None else cfg["learning_rate"]
+    thr = 1e-7 if cfg["accuracy_threshold"] is None else cfg["accuracy_threshold"]
+    if solver == "lbfgs":
+        res = OP.lbfgs(obj, x0, its, accuracy_threshold=thr, batch_size=batch, seed=cfg["seed"],
+                       step_length=cfg["step_length"] if "step_length" in cfg["named"] or batch else None)
+    elif solver == "adagrad":
+        res = OP.adagrad(obj, x0, its, lr, batch, accuracy_threshold=thr, seed=cfg["seed"])
+    else:
+        res = OP.sgd(obj, x0, its, lr, batch, thr, momentum=cfg["momentum"] if solver == "momentum" else 0.0,
+                     seed=cfg["seed"])
+    return {"minimum": res.minimum, "nIterations": torch.tensor([res.n_iterations]), "value": res.value,
+            "iterations": res.n_iterations}
 
 
 def _run_daal_pqr(comm, cfg, A):

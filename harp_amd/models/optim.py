@@ -9,7 +9,9 @@ stochastic draws; results are ``minimum`` and ``nIterations``.
 MI355X design: objectives evaluate value/gradient of the whole (or sampled) local block
 with GEMMs; in a distributed run each worker holds a row shard and the gradient of the
 sampled batch is summed across workers with ONE allreduce per step (synchronous
-data-parallel), so every worker follows the same trajectory.
+data-parallel), so every worker follows the same trajectory. ``engine="native"`` objectives
+take the local sums from the fused pass of ``csrc/glm.hip`` (``ops/glm.py``), and ``sgd`` /
+``adagrad`` on them run every iteration in one kernel launch on a single GPU.
 """
 from __future__ import annotations
 
@@ -19,6 +21,7 @@ from typing import Callable, Optional, Sequence
 
 import torch
 
+from ..ops import glm as GL
 from ..ops import linalg as LA
 
 from ..parallel.comm import Communicator
@@ -30,12 +33,30 @@ class Objective:
     """Sum over the rows of (X, y) of a per-row loss of the argument ``x``.
     ``value_grad(x, idx)`` evaluates the (global when ``comm`` is set) sum over the
     rows ``idx`` (local indices; None = all rows), divided by the global row count of
-    the batch (DAAL normalises by the batch size)."""
+    the batch (DAAL normalises by the batch size).
+
+    ``engine="native"`` takes the local sums from the fused pass of ``ops/glm.py`` (one read of
+    the block in its own dtype, fp64 sums, no [n, .] temporary; HIP kernels on a GPU, the torch
+    formulas below on the CPU). Normalisation, ``l2`` and the all-reduce are the same for both
+    engines, so row shards work unchanged."""
+
+    KIND: Optional[str] = None  # the objective's name in ops/glm.py (None: no native pass)
 
     def __init__(self, X: torch.Tensor, y: torch.Tensor, comm: Optional[Communicator] = None, l2: float = 0.0,
-                 intercept: bool = True):
+                 intercept: bool = True, engine: str = "torch"):
         self.X, self.y, self.comm, self.l2, self.intercept = X, y, comm, l2, intercept
         self.n_local = X.shape[0]
+        self._set_engine(engine, 0)
+
+    def _set_engine(self, engine: str, num_classes: int) -> None:
+        if engine not in ("torch", "native"):
+            raise ValueError(f"engine={engine!r}: expected 'torch' or 'native'")
+        if engine == "native":
+            if self.KIND is None:
+                raise ValueError(f"{type(self).__name__} has no native pass")
+            GL.check_width(self.KIND, self.X.shape[1], num_classes)
+            self._y64 = GL.targets(self.y)  # converted once, not per pass
+        self.engine = engine
 
     @property
     def dim(self) -> int:
@@ -53,8 +74,13 @@ class Objective:
     def _local(self, x, idx):
         raise NotImplementedError
 
+    def _sums(self, x, idx):
+        if self.engine == "native":
+            return GL.value_grad(self.X, self._y64, x, self.KIND, idx, getattr(self, "K", 0), self.intercept)
+        return self._local(x, idx)
+
     def value_grad(self, x: torch.Tensor, idx: Optional[torch.Tensor] = None):
-        v, g, n = self._local(x, idx)
+        v, g, n = self._sums(x, idx)
         if self.comm is not None and self.comm.world_size > 1:
             r = reduce_partials(self.comm, {"v": v.reshape(1), "g": g, "n": torch.tensor([float(n)], dtype=g.dtype,
                                                                                          device=g.device)})
@@ -75,6 +101,8 @@ class Objective:
 class MSE(Objective):
     """f_i = (x0 + x_{1..p} . X_i - y_i)^2 / 2 (daal mse)."""
 
+    KIND = "mse"
+
     def _local(self, x, idx):
         Xb, yb = (self.X, self.y) if idx is None else (self.X[idx], self.y[idx])
         r = self._lin(x, Xb.to(x.dtype)) - yb.to(x.dtype).reshape(-1)
@@ -85,6 +113,8 @@ class MSE(Objective):
 
 class LogisticLoss(Objective):
     """Binary cross-entropy of sigmoid(x0 + x.X_i) against y_i in {0, 1} (daal logistic_loss)."""
+
+    KIND = "logistic"
 
     def _local(self, x, idx):
         Xb, yb = (self.X, self.y) if idx is None else (self.X[idx], self.y[idx])
@@ -101,9 +131,13 @@ class CrossEntropyLoss(Objective):
     """Multinomial cross-entropy; the argument is the flattened [K, p+1] coefficient
     matrix (intercept column first), y holds class ids (daal cross_entropy_loss)."""
 
-    def __init__(self, X, y, num_classes: int, comm=None, l2: float = 0.0, intercept: bool = True):
+    KIND = "cross_entropy"
+
+    def __init__(self, X, y, num_classes: int, comm=None, l2: float = 0.0, intercept: bool = True,
+                 engine: str = "torch"):
         super().__init__(X, y, comm, l2, intercept)
         self.K = num_classes
+        self._set_engine(engine, num_classes)
 
     def _dim(self):
         return self.K * (self.X.shape[1] + (1 if self.intercept else 0))
@@ -172,6 +206,36 @@ class _Sampler:
         return torch.randint(0, self.n, (self.batch,), generator=self.g).to(self.dev)
 
 
+def _index_table(obj: Objective, n_iterations: int, batch_size: int, seed: int, batch_indices):
+    """The [n_iterations, batch] table of the rows a run visits, drawn up front on the host from
+    the stream :class:`_Sampler` draws step by step (same seed, same ``torch.randint`` calls, or
+    the given ``batch_indices``), when the run can take the one-launch kernel of ``ops/glm.py``:
+    a native MSE / logistic objective on a HIP device, not distributed, and a per-step batch
+    within the kernel's limit that is not the whole block. None otherwise."""
+    if (obj.engine != "native" or obj.KIND not in ("mse", "logistic") or obj.X.device.type != "cuda"
+            or (obj.comm is not None and obj.comm.world_size > 1) or n_iterations < 1 or obj.n_local < 1
+            or obj.dim > GL.SOLVER_MAX_DIM):
+        return None
+    if batch_indices is None:
+        if not 1 <= batch_size <= min(GL.SOLVER_MAX_BATCH, obj.n_local - 1):
+            return None
+    else:
+        sizes = {int(torch.as_tensor(b).numel()) for b in batch_indices}
+        if len(sizes) != 1 or not 1 <= min(sizes) <= GL.SOLVER_MAX_BATCH:
+            return None
+    sample = _Sampler(obj.n_local, batch_size, seed, torch.device("cpu"), batch_indices)
+    return torch.stack([sample(k) for k in range(n_iterations)])
+
+
+def _one_launch(obj: Objective, x0, table, method, learning_rate, dtype, **kw) -> SolverResult:
+    dev = obj.X.device
+    x = torch.zeros(obj.dim, dtype=torch.float64) if x0 is None else x0
+    lr = torch.tensor([_lr(learning_rate, k) for k in range(table.shape[0])], dtype=torch.float64)
+    x, niter = GL.run(obj.X, obj._y64, obj.KIND, obj.intercept, x, table, lr, method=method, l2=obj.l2, **kw)
+    x = x.to(dev, dtype)
+    return SolverResult(x, int(niter), float(obj.value(x)))
+
+
 def sgd(obj: Objective, x0: Optional[torch.Tensor] = None, n_iterations: int = 1000, learning_rate=0.01,
         batch_size: int = 1, accuracy_threshold: float = 0.0, momentum: float = 0.0, seed: int = 0,
         batch_indices: Optional[Sequence] = None, conservative_sequence=None, inner_iterations: int = 1,
@@ -179,7 +243,16 @@ def sgd(obj: Objective, x0: Optional[torch.Tensor] = None, n_iterations: int = 1
     """SGD family: ``batch_size=1`` -> daal sgd defaultDense; ``batch_size>1`` ->
     miniBatch (optionally with ``conservative_sequence`` proximal term and
     ``inner_iterations``); ``momentum>0`` -> momentum method. Stops when the relative
-    step ||x_{k+1}-x_k|| / max(1, ||x_k||) falls below ``accuracy_threshold``."""
+    step ||x_{k+1}-x_k|| / max(1, ||x_k||) falls below ``accuracy_threshold``.
+    A native objective on a GPU runs all iterations in one kernel launch where
+    :func:`_index_table` allows it; it visits the rows this loop would visit."""
+    table = _index_table(obj, n_iterations, batch_size, seed, batch_indices) if dtype == torch.float64 else None
+    if table is not None:
+        gamma = None
+        if conservative_sequence is not None:
+            gamma = torch.tensor([_lr(conservative_sequence, k) for k in range(n_iterations)], dtype=torch.float64)
+        return _one_launch(obj, x0, table, "sgd", learning_rate, dtype, gamma=gamma, inner=max(1, inner_iterations),
+                           momentum=momentum, threshold=accuracy_threshold)
     dev = obj.X.device
     x = (torch.zeros(obj.dim, dtype=dtype, device=dev) if x0 is None else x0.to(dev, dtype).clone())
     v = torch.zeros_like(x)
@@ -208,7 +281,12 @@ def sgd(obj: Objective, x0: Optional[torch.Tensor] = None, n_iterations: int = 1
 def adagrad(obj: Objective, x0=None, n_iterations: int = 1000, learning_rate=0.1, batch_size: int = 1,
             degenerate_cases_threshold: float = 1e-8, accuracy_threshold: float = 0.0, seed: int = 0,
             batch_indices=None, dtype=torch.float64) -> SolverResult:
-    """AdaGrad: G += g^2; x -= lr g / sqrt(G + eps) (daal adagrad)."""
+    """AdaGrad: G += g^2; x -= lr g / sqrt(G + eps) (daal adagrad). One kernel launch for a
+    native objective on a GPU, as in :func:`sgd`."""
+    table = _index_table(obj, n_iterations, batch_size, seed, batch_indices) if dtype == torch.float64 else None
+    if table is not None:
+        return _one_launch(obj, x0, table, "adagrad", learning_rate, dtype, threshold=accuracy_threshold,
+                           eps=degenerate_cases_threshold)
     dev = obj.X.device
     x = torch.zeros(obj.dim, dtype=dtype, device=dev) if x0 is None else x0.to(dev, dtype).clone()
     G = torch.zeros_like(x)

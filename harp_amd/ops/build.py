@@ -35,7 +35,8 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-f
              "-Wno-unused-result", "-I" + CSRC]
 # per source: flags on top of HIP_FLAGS (kmeans_f64 converts fp32 rows in registers and keeps the
 # compiler from pairing those operations into packed fp32 instructions)
-HIP_FILE_FLAGS = {"kmeans_f64.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+HIP_FILE_FLAGS = {"kmeans_f64.hip": _NO_PACKED_FP32, "glm.hip": _NO_PACKED_FP32}
 CXX = os.environ.get("CXX", "g++")
 CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-I" + CSRC]
 
