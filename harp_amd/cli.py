@@ -64,6 +64,11 @@ same parameters as named flags (which win when both are given):
             order), pqr_R.csv, pqr_permutation.csv. native (default): Householder TSQR and the
             d x d pivoted QR of ops/pqr.py, at most 128 columns; host: LAPACK, maps = 1
             [--engine native|host]
+            algo svd: singular value decomposition over the workers' row shards (daal_svd,
+            SVDDaalCollectiveMapper) -> svd_singularValues.csv, svd_rightSingularMatrix.csv,
+            svd_leftSingularMatrix.csv (this worker's rows). torch (default): torch.linalg.svd of
+            the d x d factor of the TSQR; native: the one-sided Jacobi kernel of ops/jsvd.py on
+            the worker's device, at most 128 columns  [--engine torch|native]
             algo optim: the optimization solvers over the workers' row shards
             (daal_optimization_solvers; last column = target) -> optim_minimum.csv (intercept
             first), optim_nIterations.csv. torch (default): models/optim.py expressions; native:
@@ -503,7 +508,11 @@ def _run_daal(comm, cfg):
         cfg = dict(cfg, algo="pqr")  # the alias writes the same file names
         out = _run_daal_pqr(comm, cfg, A)
     elif algo == "svd":
-        out = ST.svd(A, comm)
+        # the native engine is opt-in here: without --engine the run stays on the torch engine
+        engine = cfg["engine"] if "engine" in cfg["named"] else "torch"
+        if engine == "native":  # the d x d step of ops/jsvd.py, on the worker's device
+            A = A.to(comm.device)
+        out = ST.svd(A, comm, engine=engine)
     elif algo == "qr":
         out = ST.tsqr(A, comm)
     elif algo in ("linreg", "ridge"):

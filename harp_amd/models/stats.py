@@ -253,7 +253,8 @@ def pca_step2(corr: torch.Tensor, comm: Optional[Communicator] = None, metrics=N
 
 
 def pca(X, comm: Optional[Communicator] = None, method: str = "correlation",
-        n_components: Optional[int] = None, dtype: Optional[str] = None, metrics=None) -> Dict[str, torch.Tensor]:
+        n_components: Optional[int] = None, dtype: Optional[str] = None, metrics=None,
+        engine: str = "torch") -> Dict[str, torch.Tensor]:
     """PCA of the (standardized) data: eigenvalues descending + eigenvectors (rows).
 
     ``correlation``: eigen-decomposition of the distributed correlation matrix (``X`` may
@@ -261,7 +262,8 @@ def pca(X, comm: Optional[Communicator] = None, method: str = "correlation",
     ``svd``: z-score the data with global moments, distributed TSQR, SVD of R
     (the DAAL svdDense method); both yield the correlation-PCA spectrum. ``dtype``: the
     step-1 precision (see :func:`covariance`). ``metrics``: the correlation method's Gram
-    allreduce and eigenvector broadcast are recorded as collectives (bench attribution)."""
+    allreduce and eigenvector broadcast are recorded as collectives (bench attribution).
+    ``engine`` (``svd`` only; see :func:`svd`): "torch" or "native" for the SVD of R."""
     comm = _local(comm)
     if method == "correlation":
         r = correlation(X, comm, dtype=dtype, metrics=metrics)
@@ -277,7 +279,7 @@ def pca(X, comm: Optional[Communicator] = None, method: str = "correlation",
         Z = (X.double() - mom["mean"].to(X.device)) / mom["standardDeviation"].to(X.device).clamp_min(1e-300)
         qr = tsqr(Z, comm, want_q=False)
         ntot = reduce_partials(comm, {"n": torch.tensor([float(X.shape[0])], device=X.device)})["n"].item()
-        _, s, vt = torch.linalg.svd(qr["R"])
+        _, s, vt = _svd_of_r(qr["R"].to(X.device) if engine == "native" else qr["R"], False, engine)
         evals, evecs = s * s / max(ntot - 1, 1), vt
     else:
         raise ValueError(method)
@@ -386,10 +388,44 @@ def tsqr(X: torch.Tensor, comm: Optional[Communicator] = None, want_q: bool = Tr
     return out
 
 
-def svd(X: torch.Tensor, comm: Optional[Communicator] = None, want_u: bool = True) -> Dict[str, torch.Tensor]:
-    """Distributed SVD via TSQR (daal_svd 3-step): X = Q R, R = U_r S V^T, U = Q U_r."""
+def _svd_of_r(R: torch.Tensor, want_u: bool, engine: str):
+    """``(U_r or None, s, V^T)`` of the d x d factor of a TSQR. "native": the one-sided Jacobi of
+    ``ops.jsvd`` on R^T (its column j is row j of R, which is contiguous): R^T = Z S W^T, so R =
+    W S Z^T, U_r = W (always orthogonal) and V^T = Z^T; without ``want_u`` no rotation is
+    accumulated."""
+    if engine == "torch":
+        return torch.linalg.svd(R)
+    if engine != "native":
+        raise ValueError(f"engine={engine!r}: expected 'torch' or 'native'")
+    from ..ops import jsvd as JS
+
+    JS.check_width(R.shape[1])
+    if R.shape[0] != R.shape[1]:
+        raise ValueError(f"svd: the native engine needs at least as many rows as columns (R is {tuple(R.shape)}): "
+                         "use engine=\"torch\"")
+    Z, s, W, sweeps = JS.svd_small(R.double().t().contiguous(), want_w=want_u)
+    if int(sweeps) < 0:
+        raise RuntimeError(f"svd: the Jacobi iteration did not converge in {JS.MAX_SWEEPS} sweeps: use engine=\"torch\"")
+    return W, s, Z.t()
+
+
+def svd(X: torch.Tensor, comm: Optional[Communicator] = None, want_u: bool = True,
+        engine: str = "torch") -> Dict[str, torch.Tensor]:
+    """Distributed SVD via TSQR (daal_svd 3-step): X = Q R, R = U_r S V^T, U = Q U_r.
+
+    ``engine``: the SVD of the d x d factor, "torch" (``torch.linalg.svd``) or "native"
+    (``ops.jsvd``: a HIP kernel on the GPU, its torch mirror on the CPU; at most
+    ``ops.jsvd.MAX_D`` columns; the results stay on X's device, and every worker gets the same
+    bits from the same all-gathered R). An exactly zero singular value leaves a zero row in the
+    native engine's rightSingularMatrix."""
+    if engine not in ("torch", "native"):
+        raise ValueError(f"engine={engine!r}: expected 'torch' or 'native'")
+    if engine == "native":
+        from ..ops import jsvd as JS
+
+        JS.check_width(X.shape[1])  # before any pass over the rows
     r = tsqr(X, comm, want_q=want_u)
-    Ur, s, vt = torch.linalg.svd(r["R"])
+    Ur, s, vt = _svd_of_r(r["R"].to(X.device) if engine == "native" else r["R"], want_u, engine)
     out = {"singularValues": s, "rightSingularMatrix": vt}
     if want_u:
         out["leftSingularMatrix"] = r["Q"] @ Ur.to(r["Q"].device, r["Q"].dtype)
