@@ -78,6 +78,14 @@ same parameters as named flags (which win when both are given):
             [--solver sgd|minibatch|momentum|adagrad|lbfgs --objective mse|logistic
             --engine torch|native --iterations --batch-size --learning-rate
             --accuracy-threshold 1e-7 --step-length (lbfgs) --momentum 0.9 --seed 0 --point x0,..]
+            algo naive (alias nb): multinomial naive Bayes over the workers' row shards
+            (daal_naive; last column = label, or ``--format csr`` with ``--labels``) ->
+            naive_logTheta.csv, naive_logPrior.csv, naive_featureSums.csv, naive_classCounts.csv
+            and, with --test-dir (dense rows, last column = label), naive_predictions.csv. torch
+            (default): one-hot GEMM with fp32 accumulators on a GPU; native: ops/nb.py, fp64 class
+            sums in one pass over the rows and an fp64 MFMA predict with the argmax fused, at most
+            64 classes (dense input; CSR input always takes ops/csr_stats.py)
+            [--k classes --engine torch|native --test-dir]
             algo mse: value and gradient of the MSE objective at --point (default zeros;
             MSEDenseBatch) -> mse_value.csv, mse_gradient.csv, both also printed
 
@@ -520,7 +528,16 @@ def _run_daal(comm, cfg):
                               method=cfg["method"] or "normal")
     elif algo in ("naive", "nb"):
         y = A[:, -1].long()
-        out = NB.train(A[:, :-1], y, cfg["k"] or _allmax(comm, int(y.max()) + 1), comm)
+        # the native engine is opt-in here: without --engine the run stays on the torch engine
+        engine = cfg["engine"] if "engine" in cfg["named"] else "torch"
+        if engine == "native":  # ops/nb.py reads the rows in place (row stride d + 1) on the worker's device
+            A = A.to(comm.device)
+        out = NB.train(A[:, :-1], y, cfg["k"] or _allmax(comm, int(y.max()) + 1), comm, engine=engine)
+        if cfg["test_dir"]:  # last column = label, as in the training rows
+            T = torch.cat([load_dense_csv(f) for f in _files(cfg["test_dir"])]).to(A.device)
+            if T.shape[1] != A.shape[1]:
+                raise ValueError(f"test rows have {T.shape[1]} columns, training rows {A.shape[1]}")
+            out["predictions"] = NB.predict(T[:, :-1], out, engine=engine).double()
     elif algo == "kmeans":
         from .models.kmeans_csr import kmeans_init, kmeans_sparse
 

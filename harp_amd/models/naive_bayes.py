@@ -6,6 +6,11 @@ per-class feature sums + per-class counts. Here the per-class sums are one
 (one-hot)^T X GEMM on the device; one allreduce merges the partials; every worker holds
 the model. Prediction is X log(theta)^T (+ log prior): a GEMM + argmax. CSR / COO input is
 never densified: the sums and the fused product + argmax come from ``ops.csr_stats`` in fp64.
+
+``engine="native"`` (opt-in) serves dense input from ``ops.nb`` instead: fp64 class sums in one
+pass over the rows as they are, and prediction on the fp64 matrix cores with the argmax fused
+(no one-hot matrix, no fp32 accumulators, no ``[n, C]`` scores; at most 64 classes). Its
+``predict`` breaks ties to the lowest class and never lets a NaN score win.
 """
 from __future__ import annotations
 
@@ -15,6 +20,7 @@ import torch
 
 from ..ops import csr_stats as CS
 from ..ops import linalg as LA
+from ..ops import nb as NBK
 from ..parallel.comm import Communicator
 from .common import reduce_partials
 from .stats import _local
@@ -24,13 +30,21 @@ def _dense(X):
     return X.to_dense() if (X.is_sparse or X.layout == torch.sparse_csr) else X
 
 
+def _check_engine(engine: str) -> None:
+    if engine not in ("torch", "native"):
+        raise ValueError(f"engine={engine!r}: expected 'torch' or 'native'")
+
+
 def train(X: torch.Tensor, y: torch.Tensor, num_classes: int, comm: Optional[Communicator] = None,
-          alpha: float = 1.0, prior: str = "fit") -> Dict[str, torch.Tensor]:
+          alpha: float = 1.0, prior: str = "fit", engine: str = "torch") -> Dict[str, torch.Tensor]:
+    _check_engine(engine)
     comm = _local(comm)
     yl = y.reshape(-1).long().to(X.device)
     acc = torch.float64 if X.device.type == "cpu" else torch.float32
     if LA._is_sparse(X):
         sums, counts = CS.class_sums(CS.to_csr_operand(X), yl, num_classes)  # fp64, from the CSR arrays
+    elif engine == "native":
+        sums, counts = NBK.class_sums(X, yl, num_classes)  # fp64, from the rows as they are
     else:
         onehot = torch.nn.functional.one_hot(yl, num_classes).to(acc)
         sums = LA.atb(onehot, X.to(acc))
@@ -46,9 +60,12 @@ def train(X: torch.Tensor, y: torch.Tensor, num_classes: int, comm: Optional[Com
     return {"logTheta": log_theta, "logPrior": log_prior, "featureSums": p["sums"], "classCounts": p["counts"]}
 
 
-def predict(X: torch.Tensor, model: Dict[str, torch.Tensor]) -> torch.Tensor:
+def predict(X: torch.Tensor, model: Dict[str, torch.Tensor], engine: str = "torch") -> torch.Tensor:
+    _check_engine(engine)
     if LA._is_sparse(X):  # argmax fused into the sparse product: no [n, C] scores, no dense X
         return CS.spmm(CS.to_csr_operand(X), model["logTheta"].to(X.device).t(), model["logPrior"], argmax=True)
+    if engine == "native":
+        return NBK.predict(X, model["logTheta"], model["logPrior"])
     lt = model["logTheta"].to(X.device)
     Xd = _dense(X).to(lt.dtype)
     return (Xd @ lt.t() + model["logPrior"].to(X.device)).argmax(1)
