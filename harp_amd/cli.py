@@ -86,6 +86,13 @@ same parameters as named flags (which win when both are given):
             sums in one pass over the rows and an fp64 MFMA predict with the argmax fused, at most
             64 classes (dense input; CSR input always takes ops/csr_stats.py)
             [--k classes --engine torch|native --test-dir]
+            algo cov / mom / pca / linreg / ridge: covariance, low-order moments, correlation or
+            SVD PCA and linear / ridge regression (last --label-cols columns = responses) over
+            the workers' row shards (daal_cov, daal_mom, daal_pca, daal_linreg, daal_ridgereg).
+            torch (default): GEMMs over shifted row slices; native: ops/xprod.py, one fp64 pass
+            over the rows on the worker's device (MFMA Gram, sums, minimum and maximum), at most
+            256 columns for the Gram (features plus responses), any width for mom
+            [--method correlation|svd (pca) normal|qr (linreg) --engine torch|native]
             algo mse: value and gradient of the MSE objective at --point (default zeros;
             MSEDenseBatch) -> mse_value.csv, mse_gradient.csv, both also printed
 
@@ -496,12 +503,18 @@ def _run_daal(comm, cfg):
     if cfg["format"] != "dense":
         raise ValueError(f"format={cfg['format']!r}: expected 'dense' or 'csr'")
     A = torch.cat([load_dense_csv(f) for f in files]) if files else torch.zeros((0, 0), dtype=torch.float64)
+    if algo in ("cov", "covariance", "mom", "moments", "pca", "linreg", "ridge"):
+        # the native engine is opt-in here: without --engine the run stays on the torch engine
+        engine = cfg["engine"] if "engine" in cfg["named"] else "torch"
+        if engine == "native":  # ops/xprod.py reads the rows in place on the worker's device
+            d = _allmax(comm, A.shape[1])  # a worker without rows still takes part in every allreduce
+            A = (A if A.shape[0] else torch.zeros((0, d), dtype=torch.float64)).to(comm.device)
     if algo in ("cov", "covariance"):
-        out = ST.covariance(A, comm)
+        out = ST.covariance(A, comm, engine=engine)
     elif algo in ("mom", "moments"):
-        out = ST.low_order_moments(A, comm)
+        out = ST.low_order_moments(A, comm, engine=engine)
     elif algo == "pca":
-        out = ST.pca(A, comm, cfg["method"] or "correlation")
+        out = ST.pca(A, comm, cfg["method"] or "correlation", engine=engine)
     elif algo in ("quantile", "qte"):
         q = [float(v) for v in cfg["q"].split(",") if v.strip()]
         d = _allmax(comm, A.shape[1])  # a worker without rows still takes part in every allreduce
@@ -525,7 +538,7 @@ def _run_daal(comm, cfg):
         out = ST.tsqr(A, comm)
     elif algo in ("linreg", "ridge"):
         out = RG.train_linear(A[:, :-lc], A[:, -lc:], comm, ridge=1.0 if algo == "ridge" else 0.0,
-                              method=cfg["method"] or "normal")
+                              method=cfg["method"] or "normal", engine=engine)
     elif algo in ("naive", "nb"):
         y = A[:, -1].long()
         # the native engine is opt-in here: without --engine the run stays on the torch engine

@@ -31,17 +31,47 @@ def _augment(X: torch.Tensor, y: torch.Tensor, intercept: bool) -> torch.Tensor:
     return torch.cat(cols + [y2], 1)
 
 
+def _normal_native(X: torch.Tensor, y: torch.Tensor, comm: Communicator, intercept: bool):
+    """(X^T X, X^T y) of the design with the intercept column LAST, in fp64 from one pass of
+    ``ops.xprod`` over X and y as its two blocks (each read in place): the intercept row and column
+    are n and the column sums, so neither a ones column nor ``[X | 1 | y]`` is built."""
+    from ..ops import xprod as XP
+    from .stats import _check_stats_engine
+
+    _check_stats_engine("native", X, None)
+    d = X.shape[1]
+    n = X.shape[0]
+    r = XP.cross_products(X, y.reshape(n, -1) if n else y.reshape(0, y.shape[-1] if y.dim() > 1 else 1))
+    red = reduce_partials(comm, {"n": r["n"], "sum": r["sum"], "xtx": r["xtx"]}, dtype=torch.float64)
+    G, s = red["xtx"], red["sum"]
+    if not intercept:
+        return G[:d, :d], G[:d, d:]
+    XtX = torch.cat([torch.cat([G[:d, :d], s[:d, None]], 1), torch.cat([s[:d], red["n"]])[None, :]])
+    return XtX, torch.cat([G[:d, d:], s[None, d:]])
+
+
 def train_linear(X: torch.Tensor, y: torch.Tensor, comm: Optional[Communicator] = None, ridge: float = 0.0,
-                 intercept: bool = True, method: str = "normal") -> Dict[str, torch.Tensor]:
-    """Returns ``beta`` [n_responses, d(+1)] with the intercept FIRST (DAAL layout)."""
+                 intercept: bool = True, method: str = "normal", engine: str = "torch") -> Dict[str, torch.Tensor]:
+    """Returns ``beta`` [n_responses, d(+1)] with the intercept FIRST (DAAL layout).
+
+    ``engine`` (``normal`` only): "torch" (``ops.linalg.gram`` of the augmented design) or "native"
+    (the normal equations in fp64 from ``ops.xprod.cross_products``: dense bf16 / fp32 / fp64 rows
+    read in place, features plus responses at most ``ops.xprod.MAX_D``)."""
     comm = _local(comm)
     p = X.shape[1] + (1 if intercept else 0)
+    if engine not in ("torch", "native"):
+        raise ValueError(f"engine={engine!r}: expected 'torch' or 'native'")
+    if engine == "native" and method != "normal":
+        raise ValueError(f"the native engine forms the normal equations (got method={method!r}): use engine=\"torch\"")
     if method == "normal":
-        A = _augment(X, y, intercept)
-        G = reduce_partials(comm, {"g": LA.gram(A)})["g"].double()
-        XtX, Xty = G[:p, :p], G[:p, p:]
+        if engine == "native":
+            XtX, Xty = _normal_native(X, y, comm, intercept)
+        else:
+            A = _augment(X, y, intercept)
+            G = reduce_partials(comm, {"g": LA.gram(A)})["g"].double()
+            XtX, Xty = G[:p, :p], G[:p, p:]
         if ridge:
-            reg = torch.eye(p, dtype=torch.float64, device=G.device) * ridge
+            reg = torch.eye(p, dtype=torch.float64, device=XtX.device) * ridge
             if intercept:
                 reg[p - 1, p - 1] = 0.0  # the intercept is not penalised
             XtX = XtX + reg

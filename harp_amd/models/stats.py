@@ -83,10 +83,35 @@ def _shifted_sums(X: torch.Tensor, acc: torch.dtype):
     return float(n), s + n * c64, xtx
 
 
-def covariance_partial(X, dtype: Optional[str] = None) -> Dict[str, torch.Tensor]:
+def _check_stats_engine(engine: str, X, dtype: Optional[str]) -> bool:
+    """True for the native step 1 (``ops.xprod``: HIP kernels on the device, their fp64 torch mirror
+    on the CPU). It reads dense rows and implies the "fp64" policy."""
+    if engine == "torch":
+        return False
+    if engine != "native":
+        raise ValueError(f"engine={engine!r}: expected 'torch' or 'native'")
+    if dtype is not None and _policy(X, dtype) == "bf16":
+        raise ValueError("the native cross-products accumulate in fp64 (got dtype='bf16'): use engine=\"torch\"")
+    if isinstance(X, LA.FeatureMajor):
+        raise ValueError("the native cross-products read row-major rows, not a FeatureMajor block: "
+                         "use engine=\"torch\"")
+    if LA._is_sparse(X):
+        raise ValueError("the native cross-products read dense rows (the sparse branch is native already): "
+                         "use engine=\"torch\"")
+    return True
+
+
+def covariance_partial(X, dtype: Optional[str] = None, engine: str = "torch") -> Dict[str, torch.Tensor]:
     """Step 1: n, sum x, X^T X (cross-product) of the local block, at the ``dtype``
     precision (module notes above). ``X``: a row-major tensor (dense or sparse) or an
-    :class:`ops.linalg.FeatureMajor` block."""
+    :class:`ops.linalg.FeatureMajor` block. ``engine="native"``: one pass of ``ops.xprod`` over
+    the dense rows (bf16 / fp32 / fp64, read in place, at most ``ops.xprod.MAX_D`` columns) in
+    fp64, shifted by the first row as the "fp64" policy is."""
+    if _check_stats_engine(engine, X, dtype):
+        from ..ops import xprod as XP
+
+        r = XP.cross_products(X)
+        return {"n": r["n"], "sum": r["sum"], "xtx": r["xtx"]}
     mode = _policy(X, dtype)
     if isinstance(X, LA.FeatureMajor):
         if mode != "bf16":
@@ -135,11 +160,12 @@ def _timed(metrics, kind: str, op: str, nbytes: int, device):
 
 
 def covariance(X, comm: Optional[Communicator] = None, bias: bool = False,
-               dtype: Optional[str] = None, metrics=None) -> Dict[str, torch.Tensor]:
+               dtype: Optional[str] = None, metrics=None, engine: str = "torch") -> Dict[str, torch.Tensor]:
     """``metrics`` (optional :class:`utils.metrics.Metrics`): the partial-result allreduce is
-    recorded as an "allreduce" collective (op "gram") with its bytes and stream time."""
+    recorded as an "allreduce" collective (op "gram") with its bytes and stream time.
+    ``engine``: step 1, see :func:`covariance_partial`."""
     comm = _local(comm)
-    part = covariance_partial(X, dtype)
+    part = covariance_partial(X, dtype, engine)
     nbytes = sum(v.numel() for v in part.values()) * 8 if comm.world_size > 1 else 0
     with _timed(metrics, "allreduce", "gram", nbytes, comm.device):
         red = reduce_partials(comm, part, dtype=torch.float64)
@@ -147,20 +173,25 @@ def covariance(X, comm: Optional[Communicator] = None, bias: bool = False,
 
 
 def correlation(X, comm: Optional[Communicator] = None, dtype: Optional[str] = None,
-                metrics=None) -> Dict[str, torch.Tensor]:
-    r = covariance(X, comm, dtype=dtype, metrics=metrics)
+                metrics=None, engine: str = "torch") -> Dict[str, torch.Tensor]:
+    r = covariance(X, comm, dtype=dtype, metrics=metrics, engine=engine)
     sd = r["covariance"].diagonal().clamp_min(0).sqrt()
     r["correlation"] = r["covariance"] / torch.outer(sd, sd).clamp_min(1e-300)
     return r
 
 
 def low_order_moments(X: torch.Tensor, comm: Optional[Communicator] = None,
-                      dtype: Optional[str] = None) -> Dict[str, torch.Tensor]:
+                      dtype: Optional[str] = None, engine: str = "torch") -> Dict[str, torch.Tensor]:
     """DAAL low_order_moments: minimum, maximum, sum, sumSquares, sumSquaresCentered, mean,
     secondOrderRawMoment, variance, standardDeviation, variation. ``dtype`` as for
     :func:`covariance`: "bf16" sums the bf16-rounded operands in fp32, "fp32" / "fp64" sum
-    shifted row slices and accumulate in fp64 (sumSquaresCentered then has no cancellation)."""
+    shifted row slices and accumulate in fp64 (sumSquaresCentered then has no cancellation).
+    ``engine="native"``: the sums, squares, minimum and maximum from one pass of
+    ``ops.xprod.col_moments`` over the dense rows (any width, read in place) in fp64, then the
+    same combination; an empty shard takes part in every all-reduce."""
     comm = _local(comm)
+    if _check_stats_engine(engine, X, dtype):
+        return _low_order_moments_native(X, comm)
     if LA._is_sparse(X):
         return _low_order_moments_csr(X, comm)
     Xd = X
@@ -196,6 +227,30 @@ def low_order_moments(X: torch.Tensor, comm: Optional[Communicator] = None,
     Xm = Xd.double() if Xd.device.type == "cpu" else Xd.float()
     mm = reduce_partials(comm, {"min": Xm.min(0).values.double(), "negmax": -Xm.max(0).values.double()},
                          Operation.MIN, dtype=torch.float64)
+    var = ss / max(N - 1, 1)
+    sd = var.clamp_min(0).sqrt()
+    return {"minimum": mm["min"], "maximum": -mm["negmax"], "sum": sums["sum"], "sumSquares": sums["sumsq"],
+            "sumSquaresCentered": ss, "mean": mean, "secondOrderRawMoment": sums["sumsq"] / N, "variance": var,
+            "standardDeviation": sd, "variation": sd / mean}
+
+
+def _low_order_moments_native(X: torch.Tensor, comm: Communicator) -> Dict[str, torch.Tensor]:
+    """Dense native branch of :func:`low_order_moments`: the shifted sums of ``ops.xprod``, then
+    the combination of the "fp64" policy (the raw sums across ranks; the centred sum of squares
+    from per-rank centred pieces)."""
+    from ..ops import xprod as XP
+
+    r = XP.col_moments(X)
+    n = float(X.shape[0])
+    s1, s2, sc1, sc2 = r["sum"], r["sumsq"], r["shifted_sum"], r["shifted_sumsq"]
+    sums = reduce_partials(comm, {"n": r["n"], "sum": s1, "sumsq": s2}, dtype=torch.float64)
+    N = sums["n"].item()
+    mean = sums["sum"] / N
+    local_mean = s1 / max(n, 1.0)
+    ss_local = sc2 - (sc1 * sc1) / max(n, 1.0)
+    ss = reduce_partials(comm, {"ss": ss_local + n * (local_mean - mean.to(s1.device)) ** 2},
+                         dtype=torch.float64)["ss"]
+    mm = reduce_partials(comm, {"min": r["min"], "negmax": -r["max"]}, Operation.MIN, dtype=torch.float64)
     var = ss / max(N - 1, 1)
     sd = var.clamp_min(0).sqrt()
     return {"minimum": mm["min"], "maximum": -mm["negmax"], "sum": sums["sum"], "sumSquares": sums["sumsq"],
@@ -263,10 +318,14 @@ def pca(X, comm: Optional[Communicator] = None, method: str = "correlation",
     (the DAAL svdDense method); both yield the correlation-PCA spectrum. ``dtype``: the
     step-1 precision (see :func:`covariance`). ``metrics``: the correlation method's Gram
     allreduce and eigenvector broadcast are recorded as collectives (bench attribution).
-    ``engine`` (``svd`` only; see :func:`svd`): "torch" or "native" for the SVD of R."""
+    ``engine``: "torch" or "native". With ``correlation`` it selects step 1
+    (:func:`covariance_partial`); with ``svd`` the moments pass (:func:`low_order_moments`) and
+    the SVD of R (:func:`svd`)."""
     comm = _local(comm)
+    if engine not in ("torch", "native"):
+        raise ValueError(f"engine={engine!r}: expected 'torch' or 'native'")
     if method == "correlation":
-        r = correlation(X, comm, dtype=dtype, metrics=metrics)
+        r = correlation(X, comm, dtype=dtype, metrics=metrics, engine=engine)
         evals, evecs = pca_step2(r["correlation"], comm, metrics=metrics)
         order = torch.argsort(evals, descending=True)
         evals, evecs = evals[order], evecs[:, order].t()
@@ -275,7 +334,7 @@ def pca(X, comm: Optional[Communicator] = None, method: str = "correlation",
             raise ValueError("method='svd' needs the row-major data")
         if LA._is_sparse(X):
             raise ValueError("method='svd' needs the dense z-scored rows: use method='correlation' on sparse input")
-        mom = low_order_moments(X, comm, dtype=dtype)
+        mom = low_order_moments(X, comm, dtype=dtype, engine=engine)
         Z = (X.double() - mom["mean"].to(X.device)) / mom["standardDeviation"].to(X.device).clamp_min(1e-300)
         qr = tsqr(Z, comm, want_q=False)
         ntot = reduce_partials(comm, {"n": torch.tensor([float(X.shape[0])], device=X.device)})["n"].item()
