@@ -86,6 +86,12 @@ same parameters as named flags (which win when both are given):
             sums in one pass over the rows and an fp64 MFMA predict with the argmax fused, at most
             64 classes (dense input; CSR input always takes ops/csr_stats.py)
             [--k classes --engine torch|native --test-dir]
+            algo knn: k-nearest-neighbour classification (daal_knn; last column = label) of the
+            rows under --test-dir by the workers' training shards -> knn_predictions.csv,
+            knn_accuracy.csv (against the test labels, also printed). torch (default): fp64
+            distance tiles and topk; native: ops/knn_f64.py, fp64 MFMA distances with the top-k
+            fused, no distance tile, at most 256 columns and k <= 32
+            [--k 5 --engine torch|native --test-dir]
             algo cov / mom / pca / linreg / ridge: covariance, low-order moments, correlation or
             SVD PCA and linear / ridge regression (last --label-cols columns = responses) over
             the workers' row shards (daal_cov, daal_mom, daal_pca, daal_linreg, daal_ridgereg).
@@ -551,6 +557,8 @@ def _run_daal(comm, cfg):
             if T.shape[1] != A.shape[1]:
                 raise ValueError(f"test rows have {T.shape[1]} columns, training rows {A.shape[1]}")
             out["predictions"] = NB.predict(T[:, :-1], out, engine=engine).double()
+    elif algo == "knn":
+        out = _run_daal_knn(comm, cfg, A)
     elif algo == "kmeans":
         from .models.kmeans_csr import kmeans_init, kmeans_sparse
 
@@ -585,6 +593,32 @@ def _run_daal(comm, cfg):
     else:
         raise ValueError(f"unknown daal algo {algo}")
     return _save_daal(comm, cfg, out)
+
+
+def _run_daal_knn(comm, cfg, A):
+    """kNN classification of the rows under --test-dir by the workers' training shards
+    (daal_knn): every worker answers all test rows from its shard, the candidates merge in
+    ``KNNClassifier``. Accuracy against the test labels is printed as the reference mapper does."""
+    from .models.kernels import KNNClassifier
+    from .utils.datasets import load_dense_csv
+
+    if not cfg["test_dir"]:
+        raise ValueError("algo=knn needs --test-dir (rows like the training rows, last column = label)")
+    # the native engine is opt-in here: without --engine the run stays on the torch engine
+    engine = cfg["engine"] if "engine" in cfg["named"] else "torch"
+    if engine == "native":  # ops/knn_f64.py reads the rows in place (row stride d + 1) on the worker's device
+        A = A.to(comm.device)
+    T = torch.cat([load_dense_csv(f) for f in _files(cfg["test_dir"])]).to(A.device)
+    if T.shape[1] != A.shape[1]:
+        raise ValueError(f"test rows have {T.shape[1]} columns, training rows {A.shape[1]}")
+    y = A[:, -1].long()
+    classes = _allmax(comm, max(int(y.max()), int(T[:, -1].max())) + 1)
+    model = KNNClassifier(cfg["k"] or 5, comm if comm.world_size > 1 else None, engine=engine)
+    pred = model.fit(A[:, :-1], y, num_classes=classes).predict(T[:, :-1]).cpu()
+    acc = float((pred == T[:, -1].long().cpu()).double().mean())
+    if comm.rank == 0:
+        print(f"knn accuracy: {acc:.6f} ({pred.numel()} test rows, k = {model.k})")
+    return {"predictions": pred.double(), "accuracy": torch.tensor([acc], dtype=torch.float64)}
 
 
 def _run_daal_outlier(comm, cfg, A):

@@ -112,17 +112,36 @@ def rbf_kernel(X, Y, sigma: float = 1.0) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------- kNN
-def knn_search(train: torch.Tensor, queries: torch.Tensor, k: int, tile: int = 8192) -> Tuple[torch.Tensor, torch.Tensor]:
+def _knn_native(train, queries, k, operand=None):
+    """The fp64 engine (``ops/knn_f64.py``) behind ``engine="native"``, its limits named."""
+    from ..ops import knn_f64 as KF
+
+    if any(X.layout != torch.strided for X in (train, queries)):
+        raise ValueError("the native fp64 kNN reads dense rows (got a sparse input): use engine=\"torch\"")
+    KF.check_width(train.shape[1])
+    KF.check_k(k)
+    return KF.knn_search(train, queries, k, operand=operand)
+
+
+def knn_search(train: torch.Tensor, queries: torch.Tensor, k: int, tile: int = 8192,
+               engine: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
     """Exact k nearest training rows of each query: (sq distances [M, k], indices [M, k]).
 
-    Dense fp32 rows on a HIP device go through the fused GEMM + top-k selection kernel
-    (``ops/knn.py``, ``csrc/knn.hip``); sparse / other-dtype / CPU inputs use the torch
-    expression below."""
+    ``engine="auto"``: dense fp32 rows on a HIP device go through the fused GEMM + top-k
+    selection kernel (``ops/knn.py``, ``csrc/knn.hip``); sparse / other-dtype / CPU inputs use
+    the torch expression below. ``"torch"`` forces that expression. ``"native"``: dense bf16 /
+    fp32 / fp64 rows go to the fp64 MFMA search with the top-k fused (``ops/knn_f64.py``,
+    ``csrc/knn_f64.hip``: fp64 distances, ties to the lower index, no distance tile, at most 256
+    columns and k <= 32) on a HIP device, and to its torch mirror on the CPU."""
     from ..ops import knn as knn_ops
 
+    if engine not in ("auto", "torch", "native"):
+        raise ValueError(f"engine={engine!r}: expected 'auto', 'torch' or 'native'")
+    if engine == "native":
+        return _knn_native(train, queries, k)
     dense = not (train.is_sparse or queries.is_sparse or train.layout == torch.sparse_csr
                  or queries.layout == torch.sparse_csr)
-    if (dense and queries.device.type == "cuda" and train.dtype == torch.float32
+    if (engine == "auto" and dense and queries.device.type == "cuda" and train.dtype == torch.float32
             and queries.dtype == torch.float32 and min(k, train.shape[0]) <= knn_ops.MAX_NATIVE_K):
         return knn_ops.knn_search(train, queries, k)
     n = train.shape[0]
@@ -141,20 +160,31 @@ class KNNClassifier:
     """kNN classifier (daal kdtree_knn_classification semantics: majority vote of the
     k nearest training points, ties to the smallest label). ``comm`` distributes the
     training set: each worker's shard answers the queries locally, candidates are
-    merged with one allgather."""
+    merged with one allgather. ``engine`` as in :func:`knn_search`; with ``"native"`` ``fit``
+    prepares the sweep operand of the shard once and every ``kneighbors`` reuses it."""
 
-    def __init__(self, k: int = 5, comm: Optional[Communicator] = None):
-        self.k, self.comm = k, comm
+    def __init__(self, k: int = 5, comm: Optional[Communicator] = None, engine: str = "auto"):
+        if engine not in ("auto", "torch", "native"):
+            raise ValueError(f"engine={engine!r}: expected 'auto', 'torch' or 'native'")
+        self.k, self.comm, self.engine = k, comm, engine
+        self._operand = None
 
     def fit(self, X, y, num_classes: Optional[int] = None):
         self.X, self.y = X, y.long().reshape(-1)
+        if self.engine == "native":
+            from ..ops import knn_f64 as KF
+
+            self._operand = KF.prepare(X)
         self.C = num_classes or int(self.y.max()) + 1
         if self.comm is not None and self.comm.world_size > 1:
             self.C = int(reduce_partials(self.comm, {"c": torch.tensor([float(self.C)])}, op=_max())["c"][0])
         return self
 
     def kneighbors(self, Q):
-        d, i = knn_search(self.X, Q, self.k)
+        if self.engine == "native":
+            d, i = _knn_native(self.X, Q, self.k, operand=self._operand)
+        else:
+            d, i = knn_search(self.X, Q, self.k, engine=self.engine)
         lab = self.y.to(i.device)[i]
         if self.comm is None or self.comm.world_size == 1:
             return d, lab
