@@ -92,6 +92,14 @@ same parameters as named flags (which win when both are given):
             distance tiles and topk; native: ops/knn_f64.py, fp64 MFMA distances with the top-k
             fused, no distance tile, at most 256 columns and k <= 32
             [--k 5 --engine torch|native --test-dir]
+            algo em: EM for a Gaussian mixture (daal_em) over the workers' row shards ->
+            em_weights.csv, em_means.csv, em_covariances.csv (one block per component, in
+            component order), em_loglik.csv, em_nIterations.csv. auto (default): the fp64 HIP
+            E-step and statistics kernels of ops/gmm.py on a GPU, torch on the CPU; torch: the
+            torch expressions; native: ops/gmm_f64.py, the E-step and the statistics fused on
+            the fp64 MFMA with no n x K responsibilities, rows read in place, at most 64
+            columns and 1024 components
+            [--k 2 --method full|diag --accuracy-threshold 1e-6 --seed 0 --engine auto|torch|native]
             algo cov / mom / pca / linreg / ridge: covariance, low-order moments, correlation or
             SVD PCA and linear / ridge regression (last --label-cols columns = responses) over
             the workers' row shards (daal_cov, daal_mom, daal_pca, daal_linreg, daal_ridgereg).
@@ -559,6 +567,8 @@ def _run_daal(comm, cfg):
             out["predictions"] = NB.predict(T[:, :-1], out, engine=engine).double()
     elif algo == "knn":
         out = _run_daal_knn(comm, cfg, A)
+    elif algo == "em":
+        out = _run_daal_em(comm, cfg, A)
     elif algo == "kmeans":
         from .models.kmeans_csr import kmeans_init, kmeans_sparse
 
@@ -619,6 +629,29 @@ def _run_daal_knn(comm, cfg, A):
     if comm.rank == 0:
         print(f"knn accuracy: {acc:.6f} ({pred.numel()} test rows, k = {model.k})")
     return {"predictions": pred.double(), "accuracy": torch.tensor([acc], dtype=torch.float64)}
+
+
+def _run_daal_em(comm, cfg, A):
+    """EM for a Gaussian mixture over the workers' row shards (daal_em): weights, means, one
+    covariance block per component in component order, the mean log-likelihood of the last
+    iteration and the iterations run."""
+    from .models.kernels import em_gmm
+
+    # the native engine is opt-in here: without --engine the run is engine="auto"
+    engine = cfg["engine"] if "engine" in cfg["named"] else "auto"
+    kind = cfg["method"] or "full"
+    if kind not in ("full", "diag"):
+        raise ValueError(f"method={kind!r}: expected 'full' or 'diag'")
+    d = _allmax(comm, A.shape[1])  # a worker without rows still takes part in every allreduce
+    if A.shape[0] == 0:
+        A = torch.zeros((0, d), dtype=torch.float64)
+    if engine == "native":  # ops/gmm_f64.py reads the rows in place on the worker's device
+        A = A.to(comm.device)
+    thr = 1e-6 if cfg["accuracy_threshold"] is None else cfg["accuracy_threshold"]
+    m = em_gmm(A, cfg["k"] or 2, comm if comm.world_size > 1 else None, n_iterations=cfg["iterations"],
+               accuracy_threshold=thr, covariance=kind, seed=cfg["seed"], engine=engine)
+    return {"weights": m["weights"], "means": m["means"], "covariances": m["covariances"].reshape(-1, d),
+            "loglik": m["loglik"].reshape(1), "nIterations": torch.tensor([float(m["n_iterations"])])}
 
 
 def _run_daal_outlier(comm, cfg, A):

@@ -218,23 +218,45 @@ def _max():
 # ---------------------------------------------------------------- EM-GMM
 def em_gmm(X: torch.Tensor, K: int, comm: Optional[Communicator] = None, n_iterations: int = 100,
            accuracy_threshold: float = 1e-6, reg: float = 1e-6, covariance: str = "full",
-           init: Optional[Dict[str, torch.Tensor]] = None, seed: int = 0, estep: str = "auto") -> Dict[str, torch.Tensor]:
+           init: Optional[Dict[str, torch.Tensor]] = None, seed: int = 0, estep: str = "auto",
+           engine: str = "auto") -> Dict[str, torch.Tensor]:
     """EM for a K-component Gaussian mixture (full or diagonal covariance).
     Distributed: each worker holds a row shard; sufficient statistics are allreduced.
     Stops when the log-likelihood improves by less than ``accuracy_threshold``.
-    ``estep``: "auto" (HIP kernels for fp64 GPU data, d <= 64) or "torch"."""
+    ``estep``: "auto" (HIP kernels for fp64 GPU data, d <= 64) or "torch".
+
+    ``engine="auto"`` is the above; ``"torch"`` forces the torch expressions (as ``estep="torch"``
+    does). ``"native"``: dense bf16 / fp32 / fp64 rows are read in place, never copied to fp64,
+    by the fp64 MFMA engine (``ops/gmm_f64.py``, ``csrc/gmm_f64.hip``: E-step and statistics
+    fused, no n x K responsibilities, bitwise repeatable, at most 64 columns and 1024 components)
+    on a HIP device, and by its torch mirror on the CPU. Diagonal covariances run through the
+    same kernels with a diagonal whitening matrix and keep the Gram's diagonal: correct, not
+    tuned."""
     from ..parallel.partition_util import broadcast_objects
 
-    Xd = _dense(X).double()
+    if engine not in ("auto", "torch", "native"):
+        raise ValueError(f"engine={engine!r}: expected 'auto', 'torch' or 'native'")
+    f64 = engine == "native"
+    if f64:
+        from ..ops import gmm_f64 as GF
+
+        if X.layout != torch.strided:
+            raise ValueError("the native fp64 EM reads dense rows (got a sparse input): use engine=\"auto\"")
+        Xd = GF.rows(X)  # in its own dtype; another layout is copied once, not in every iteration
+        GF.check_shape(Xd.shape[1], K, Xd.shape[0])
+    else:
+        Xd = _dense(X).double()
+    if engine == "torch":
+        estep = "torch"
     n, d = Xd.shape
     dev = Xd.device
     if init is None:
         g = torch.Generator().manual_seed(seed)
-        cand = Xd[torch.randperm(n, generator=g)[:K].to(dev)]
+        cand = Xd[torch.randperm(n, generator=g)[:K].to(dev)].double()
         if comm is not None and comm.world_size > 1:
             cand = broadcast_objects(comm, [cand.cpu()] if comm.rank == 0 else None)[0].to(dev)
-        mom = reduce_partials(comm or _one(), {"n": torch.tensor([float(n)]), "s": Xd.sum(0).cpu(),
-                                               "ss": (Xd * Xd).sum(0).cpu()})
+        s, ss = GF.column_moments(Xd) if f64 else (Xd.sum(0), (Xd * Xd).sum(0))
+        mom = reduce_partials(comm or _one(), {"n": torch.tensor([float(n)]), "s": s.cpu(), "ss": ss.cpu()})
         var = (mom["ss"] / mom["n"] - (mom["s"] / mom["n"]) ** 2).to(dev)
         w = torch.full((K,), 1.0 / K, dtype=torch.float64, device=dev)
         mu = cand.clone()
@@ -246,11 +268,13 @@ def em_gmm(X: torch.Tensor, K: int, comm: Optional[Communicator] = None, n_itera
     it = 0
     from ..ops import gmm as GM
 
-    native = GM.usable(Xd) and estep != "torch"
+    native = not f64 and GM.usable(Xd) and estep != "torch"
     if native:
         Xd = GM.row_major(Xd)  # a strided view is copied once, not in every iteration
     for it in range(n_iterations):
-        if native:
+        if f64:
+            Nk, S1, S2, llsum = GF.estep_stats(Xd, w, mu, cov, covariance)
+        elif native:
             R, llsum = GM.estep(Xd, w, mu, cov, covariance)
             Nk, S1, S2 = GM.stats(Xd, R, covariance)
         else:
@@ -297,9 +321,20 @@ def _log_gauss(X, mu, cov, covariance):
     return -0.5 * (maha + logdet[None, :] + d * math.log(2 * math.pi))
 
 
-def gmm_predict(X, model) -> torch.Tensor:
+def gmm_predict(X, model, engine: str = "auto") -> torch.Tensor:
+    """The most likely component of every row. ``engine="native"``: the E-step kernel of
+    ``ops/gmm_f64.py`` with the arg-max fused (ties to the lowest component, a NaN never wins, no
+    [n, K] tensor); ``"auto"`` and ``"torch"``: the torch expression."""
+    if engine not in ("auto", "torch", "native"):
+        raise ValueError(f"engine={engine!r}: expected 'auto', 'torch' or 'native'")
     cov = model["covariances"]
     kind = "full" if cov.dim() == 3 else "diag"
+    if engine == "native":
+        from ..ops import gmm_f64 as GF
+
+        if X.layout != torch.strided:
+            raise ValueError("the native fp64 EM reads dense rows (got a sparse input): use engine=\"auto\"")
+        return GF.predict(GF.rows(X), model["weights"], model["means"], cov, kind)
     return (_log_gauss(_dense(X).double(), model["means"], cov, kind) + torch.log(model["weights"])[None]).argmax(1)
 
 

@@ -36,7 +36,8 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-f
 # per source: flags on top of HIP_FLAGS (kmeans_f64 converts fp32 rows in registers and keeps the
 # compiler from pairing those operations into packed fp32 instructions)
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-HIP_FILE_FLAGS = {"kmeans_f64.hip": _NO_PACKED_FP32, "glm.hip": _NO_PACKED_FP32, "knn_f64.hip": _NO_PACKED_FP32}
+HIP_FILE_FLAGS = {"kmeans_f64.hip": _NO_PACKED_FP32, "glm.hip": _NO_PACKED_FP32, "knn_f64.hip": _NO_PACKED_FP32,
+                  "gmm_f64.hip": _NO_PACKED_FP32}
 CXX = os.environ.get("CXX", "g++")
 CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-I" + CSRC]
 
